@@ -1,7 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- rows/s per training iteration on MI355X (BASELINE.json metric).
 
-A default run times all four BASELINE workloads, one after the other, each
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+figure needs and no more: it builds the KMeans workload's data, warms up,
+times the N steps and prints the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, and the roofline of the kernels timed
+with HIP events inside those steps).  --dump-outputs DIR also writes what the
+last timed step computed (see dump_outputs).  --workload NAME times another
+workload the same lean way; --workload all every one of them.
+
+--full adds everything else, as one run: all five workloads plus the blas leg
+(unless --workload names one), each with its CPU baseline (cpu_baseline), the
+whole fit beside the steady-state steps (fit), the comparisons timed after
+the clock (KMeans's full cluster-sums pass, the PCA's centred form and host
+SVD), the unpriced kernels' times (diag_kernels_ms_per_step) and the counted
+passes behind the roofline's extra fields.
+
+--steps and --warmup set the steps of the first (headline) workload of the
+run; each workload after it takes at most 20 timed and 5 warm-up steps and
+says so in its own "steps" / "warmup" fields.
+
+With --full the workloads run one after the other, each
 with its own data resident in HBM and freed before the next:
   kmeans       (headline, BASELINE configs[1], the config the metric is
                quoted on) KMeans k=1024 on synthetic dense fp64 10M x 256, one
@@ -15,9 +34,8 @@ with its own data resident in HBM and freed before the next:
                50M rows); one RDDLossFunction.calculate per step
   lr_sparse    binomial LR on CSR, 1M features, 64 nnz/row (configs[4]: 200M
                rows, tiles layout); one RDDLossFunction.calculate per step
-The headline JSON line is KMeans's; the other three ride along under
-"workloads", each with its own value, roofline and cpu_baseline.
---workload NAME times one of them alone.
+The headline JSON line is KMeans's; with --full (or --workload all) the
+others ride along under "workloads", each with its own value and roofline.
 
 Rows per GPU (--scaling auto): KMeans config 2 is a one-GPU config, so each
 GPU holds 10M rows (weak scaling); configs 3-5 are totals split over the N
@@ -35,10 +53,10 @@ kernel (the priced kernel with the most time per step), timed with HIP
 events on the stream it runs on inside the timed region (cyc_profile_*),
 lists every priced kernel's fraction under `priced_kernels`, and carries
 `step_frac`: the workload's algorithmic work per step (`step_work`) over
-`ms_per_step`, against the same kind of peak; `cpu_baseline` is the CPU
+`ms_per_step`, against the same kind of peak; `cpu_baseline` (--full) is the CPU
 restatement (oracle/, a C port of the reference loops) on a bounded sample of
-the same data, one partition per available host core.  On one GPU a `blas`
-leg follows: the per-call netlib layer (libcyclone_blas.so) at
+the same data, one partition per available host core.  On one GPU, with
+--full, a `blas` leg follows: the per-call netlib layer (libcyclone_blas.so) at
 BLASBenchmark's shapes against its published rates.
 """
 from __future__ import annotations
@@ -61,6 +79,10 @@ HBM = ("hbm", "GB/s", HBM_PEAK_GBS, 1e9)
 FP64 = ("mfma", "TFLOP/s", FP64_PEAK_TFLOPS, 1e12)
 I8 = ("mfma", "TOPS", I8_PEAK_TOPS, 1e12)
 
+# steps / warm-up steps of a workload that rides along behind the headline
+# (--full, --workload all): the whole run stays within minutes whatever
+# --steps asks of the headline
+RIDER_STEPS, RIDER_WARMUP = 20, 5
 DIST_BACKEND = "gloo"     # torch.distributed's group: host only, no second RCCL communicator
 ORDER = ("kmeans", "gramian", "pca", "lr_multi", "lr_sparse")
 # BASELINE configs: rows of the whole problem, and whether it is per GPU
@@ -79,12 +101,25 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--workload", default="all", choices=("all",) + ORDER + ("blas",))
+    ap.add_argument("--workload", default=None, choices=("all",) + ORDER + ("blas",),
+                    help="default: kmeans (the headline); with --full: all")
+    ap.add_argument("--full", action="store_true",
+                    help="also the other workloads, CPU baselines, whole fits, the comparisons "
+                         "and diagnostic passes timed after the clock")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<workload>_<name>.npy")
     ap.add_argument("--scaling", default="auto", choices=("auto", "weak", "strong"))
     ap.add_argument("--rows", type=int, default=0, help="rows per GPU (0 = from --scaling)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target CPU time of each cpu_baseline sample (0 disables)")
+                    help="with --full: target CPU time of each cpu_baseline sample "
+                         "(0 disables)")
     return ap.parse_args(argv)
+
+
+def rider_args(args):
+    """`args` for a workload that rides along behind the headline."""
+    return argparse.Namespace(**{**vars(args), "steps": min(args.steps, RIDER_STEPS),
+                                 "warmup": min(args.warmup, RIDER_WARMUP)})
 
 
 def rows_per_gpu(workload, scaling, world, rank, override=0):
@@ -179,6 +214,35 @@ def timed_parallel(fn, parts, threads):
     with ThreadPoolExecutor(threads) as ex:
         out = list(ex.map(fn, parts))
     return time.perf_counter() - t0, out
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # all of one run's --dump-outputs files together
+_dumped_bytes = 0
+
+
+def dump_outputs(directory, workload, arrays):
+    """--dump-outputs: write `arrays` (name -> device tensor, numpy array or
+    scalar: what a caller of the timed path receives from its last timed
+    step) as directory/<workload>_<name>.npy, float64 (float32 arrays stay
+    float32).  The inputs are seeded, so two builds run with the same
+    arguments can be compared file by file.  An array that would take the
+    run past DUMP_LIMIT_BYTES is cut to a fixed sample: the elements at
+    numpy PCG64 (seed 0) positions of its flattened form, in index order."""
+    global _dumped_bytes
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        room = max(DUMP_LIMIT_BYTES - _dumped_bytes - 4096 * (len(arrays) + 1), 0)
+        if a.nbytes > room:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, room // a.itemsize,
+                                                          replace=False))
+            a = a.reshape(-1)[idx]
+        a = np.ascontiguousarray(a)
+        _dumped_bytes += a.nbytes + 128          # .npy header
+        np.save(os.path.join(directory, f"{workload}_{name}.npy"), a)
 
 
 # ------------------------------------------------------------ synthetic data
@@ -351,6 +415,15 @@ class KMeansWorkload:
         inc, moved = self.rows.incremental_info()
         self.inc_timed = inc - self._i0[0]
         self.moved_timed = moved - self._i0[1]
+        self._refine = self.plan.last_refine()
+
+    def outputs(self):
+        """The last step's merged sums, weights and cost, and the centers
+        (with their norms and the convergence flag) its update left."""
+        k, d = self.k, self.d
+        return {"centers": self.C, "center_norms": self.cnorm,
+                "sums": self.buf[:k * d].reshape(k, d), "weights": self.buf[k * d:k * d + k],
+                "cost": self.buf[k * d + k:], "converged": self.conv}
 
     def step(self):
         k, d = self.k, self.d
@@ -416,7 +489,6 @@ class KMeansWorkload:
 
     def after_timing(self):
         import torch
-        self._refine = self.plan.last_refine()
         # the same steps with the full cluster-sums pass every step (the
         # incremental sums off), for comparison; then back on (the fit)
         self.rows.set_incremental(False)
@@ -553,6 +625,9 @@ class GramianWorkload:
         self.plan.accumulate(self.X, self.U)
         self.parallel.allreduce_(self.U)
 
+    def outputs(self):
+        return {"gramian_upper": self.U}
+
     def work(self, kname, launches_per_step):
         return float(self.n) * self.p * (self.p + 1) / launches_per_step, FP64   # flops (upper)
 
@@ -617,6 +692,9 @@ class PCAWorkload:
 
     def step(self):
         self.G = self.mat.computeCovarianceDevice()
+
+    def outputs(self):
+        return {"covariance": self.G}
 
     def work(self, kname, launches_per_step):
         if kname == "k_col_sums":             # the rows its passes read once (fp64)
@@ -717,7 +795,10 @@ class LRMultiWorkload:
             inv_std, sm_dev, True, True, c, device=dev))
 
     def step(self):
-        self.fn.calculate(self.coef)
+        self.out = self.fn.calculate(self.coef)
+
+    def outputs(self):
+        return {"loss": self.out[0], "gradient": self.out[1]}
 
     def fit_once(self, max_iter=20):
         """One LogisticRegression.fit as the reference runs it on these rows
@@ -829,7 +910,10 @@ class LRSparseWorkload:
             inv_std, sm_dev, True, True, c, device=dev))
 
     def step(self):
-        self.fn.calculate(self.coef)
+        self.out = self.fn.calculate(self.coef)
+
+    def outputs(self):
+        return {"loss": self.out[0], "gradient": self.out[1]}
 
     def work(self, kname, launches_per_step):
         if kname == "k_tiles_rows":           # the rows' epilogue: dot + label in, multiplier out
@@ -975,6 +1059,12 @@ def run_blas(args, cpu_seconds):
                        "vs_java": rate / java, "vs_native": rate / native,
                        "published_source": f"BLASBenchmark-jdk17-results.txt:{lines}"}
     el = time.perf_counter() - t_all
+    if args.dump_outputs:
+        # the iterations drop their results (the benchmark's clones): the
+        # headline routine's call once more, on the same operands
+        Cout = Cg.copy()
+        nb.dgemm("N", "N", g, g, g, a, Ag, g, Bg, g, b, Cout, g)
+        dump_outputs(args.dump_outputs, "blas", {"dgemm_nn": Cout})
     del L
     # the oracle's netlib restatements on one host core, same shapes (a
     # netlib call is single-threaded: docs/ml-linalg-guide.md:79-91)
@@ -1073,11 +1163,15 @@ def run_workload(name, args, dev, rank, world, cpu_seconds):
     prof = {kname: N.profile_query(kname) for kname in kernels}
     N.profile_enable(False)
     N.profile_only(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, name, wl.outputs())
     el = parallel.max_over_ranks(el, dev)
     value = total_rows * args.steps / el
+    # From here to the result dict, --full only: passes of their own after
+    # the clock (they also move the workload's state past the dumped step).
     diag = {}
     rest = [k for k in kernels if k not in priced]
-    if rest and os.environ.get("CYC_BENCH_NO_EVENTS") != "1":
+    if args.full and rest and os.environ.get("CYC_BENCH_NO_EVENTS") != "1":
         dsteps = min(3, args.steps)
         N.profile_only(rest)
         N.profile_enable(True)
@@ -1090,10 +1184,10 @@ def run_workload(name, args, dev, rank, world, cpu_seconds):
         N.profile_enable(False)
         N.profile_only(None)
 
-    if hasattr(wl, "after_timing"):
+    if args.full and hasattr(wl, "after_timing"):
         wl.after_timing()
     fit = None
-    if hasattr(wl, "fit_once"):
+    if args.full and hasattr(wl, "fit_once"):
         # a whole fit beside the steady-state iterations (same clock rules)
         if world > 1:
             dist.barrier()
@@ -1138,9 +1232,9 @@ def run_workload(name, args, dev, rank, world, cpu_seconds):
     kms, launches = prof[kname]
     avg_s = kms / max(launches, 1) / 1e3
     extra = wl.extra_roofline(launches / args.steps, avg_s) if (
-        launches and hasattr(wl, "extra_roofline")) else {}
+        args.full and launches and hasattr(wl, "extra_roofline")) else {}
     cpu = None
-    if rank == 0 and world == 1 and cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and cpu_seconds > 0:
         cpu = wl.cpu_baseline(cpu_seconds)
         cpu["host"] = _cores_info()
     out = {
@@ -1219,17 +1313,26 @@ def main():
     comm = parallel.init(dev)          # libcyclone's RCCL communicator (cyc_comm_*)
     if comm is not None:
         world = comm.world_size        # n_gpus as the live communicator reports it
-    names = ORDER if args.workload == "all" else (args.workload,)
-    if args.workload == "all" and world == 1:
+    workload = args.workload or ("all" if args.full else ORDER[0])
+    names = ORDER if workload == "all" else (workload,)
+    if workload == "all" and args.full and world == 1:
         names = names + ("blas",)     # the per-call layer: one process, host operands
     results = {}
     for name in names:
         t0 = time.perf_counter()
         cpu_s = args.cpu_seconds if name == names[0] else min(args.cpu_seconds, 8.0)
+        if not args.full:
+            cpu_s = 0.0
+        wargs = args
+        if name != names[0]:
+            # --steps / --warmup are the headline's: a workload that rides along
+            # (0.2-0.5 s per step, the blas leg 13 routines per iteration) takes
+            # at most RIDER_STEPS / RIDER_WARMUP of them and reports its own count
+            wargs = rider_args(args)
         if name == "blas":
-            results[name] = run_blas(args, cpu_s)
+            results[name] = run_blas(wargs, cpu_s)
         else:
-            results[name] = run_workload(name, args, dev, rank, world, cpu_s)
+            results[name] = run_workload(name, wargs, dev, rank, world, cpu_s)
         if rank == 0:
             print(f"[bench] {name}: {results[name]['value'] / 1e6:.1f} M rows/s, "
                   f"{results[name]['ms_per_step']:.2f} ms/step "

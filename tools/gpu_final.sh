@@ -17,11 +17,14 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun
 tail -1 gpurun_out/smoke.log
 fi
 if [ $PART != tests ]; then
-# the driver's command: every workload in one run, KMeans as the headline line
-timeout -k 10 500 python -u bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} > gpurun_out/bench_all.json 2> gpurun_out/bench_all.err || { echo BENCH FAIL; tail -20 gpurun_out/bench_all.err; exit 1; }
+# every workload with its CPU baseline and fit in one run (--full), KMeans as
+# the headline line; written under $BENCH_OUT (default: bench_out/)
+export BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p $BENCH_OUT
+timeout -k 10 500 python -u bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $BENCH_OUT/bench_all.json 2> $BENCH_OUT/bench_all.err || { echo BENCH FAIL; tail -20 $BENCH_OUT/bench_all.err; exit 1; }
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/bench_all.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.environ["BENCH_OUT"] + "/bench_all.json").read().strip().splitlines()[-1])
 for name, w in [("kmeans", d)] + list(d.get("workloads", {}).items()):
     r = w.get("roofline") or {}
     print(name, round(w["value"] / 1e6, 1), "M/s", round(w["ms_per_step"], 2), "ms",
