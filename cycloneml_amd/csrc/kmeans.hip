@@ -103,9 +103,12 @@ __global__ void k_center_transpose(const double* __restrict__ C, int k, int d, i
   Ct[idx] = (i < k && j < d) ? C[(int64_t)i * d + j] : 0.0;
 }
 
-constexpr unsigned long long kInfBits = 0x7FF0000000000000ull;   // +Infinity
-constexpr int kStT = 32;    // centers per statistics tile side
-constexpr int kStC = 32;    // dimensions per LDS chunk of the statistics
+// kInfBits, the statistics' tile sizes and the bodies of the center kernels
+// below live in kmeans_i8.hpp (cyc::kmc): centers_prepare_all runs the same
+// bodies as jobs of its fused launches.
+using cyc::kmc::kInfBits;
+using cyc::kmc::kStT;
+using cyc::kmc::kStC;
 
 __global__ void k_fill_u64(unsigned long long* __restrict__ p, int n, unsigned long long v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -115,100 +118,23 @@ __global__ void k_fill_u64(unsigned long long* __restrict__ p, int n, unsigned l
 __global__ void k_center_transpose_fill(const double* __restrict__ C, int k, int d, int d4,
                                         int kpad, double* __restrict__ Ct,
                                         unsigned long long* __restrict__ p, unsigned long long v) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx < k) p[idx] = v;
-  const int64_t total = (int64_t)d4 * kpad;
-  if (idx >= total) return;
-  const int j = (int)(idx / kpad), i = (int)(idx % kpad);
-  Ct[idx] = (i < k && j < d) ? C[(int64_t)i * d + j] : 0.0;
+  cyc::kmc::center_transpose_fill(C, k, d, d4, kpad, Ct, p, v, blockIdx.x, threadIdx.x);
 }
 // two counters zeroed by one launch (two fills before)
 __global__ void k_zero2(unsigned int* __restrict__ a, unsigned int* __restrict__ b) {
-  if (threadIdx.x == 0) *a = 0u;
-  if (threadIdx.x == 1 && b) *b = 0u;
+  cyc::kmc::zero2(a, b, threadIdx.x);
 }
 
-// computeStatistics pairs (DistanceMeasure.scala:55-66, Euclidean :275-277):
-// s = 0.25 * distance * distance, distance = Math.sqrt(sqdist(c_i, c_j)).
-// One workgroup per 32 x 32 tile of the upper block triangle: 32-dimension
-// chunks of both center tiles in LDS, 2 x 2 pairs per thread, every pair's
-// sum sequential over the dimensions in order (bit-exact).  The row minima
-// of the diagonal (:62-63) go to dmin as fp64 bit patterns: a statistic is
-// >= +0 or NaN, and for those the unsigned bit order is the value order with
-// every NaN above +Infinity, so atomicMin never keeps a NaN -- just as the
-// reference's `if (s < diagValues(i))` skips it.
+// computeStatistics pairs and diagonal (cyc::kmc::stats_pairs / stats_diag)
 __global__ __launch_bounds__(256) void k_stats_pairs(const double* __restrict__ C, int k, int d,
                                                      int tps, double* __restrict__ packed,
                                                      unsigned long long* __restrict__ dmin) {
-  __shared__ double Ci[kStT][kStC + 1], Cj[kStT][kStC + 1];
-  __shared__ unsigned long long rmin[kStT], cmin[kStT];
-  int t = blockIdx.x, bi = 0;
-  while (t >= tps - bi) {
-    t -= tps - bi;
-    ++bi;
-  }
-  const int bj = bi + t;
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  if (threadIdx.x < kStT) rmin[threadIdx.x] = cmin[threadIdx.x] = kInfBits;
-  double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
-  for (int c0 = 0; c0 < d; c0 += kStC) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < kStT * kStC; e += 256) {
-      const int r = e >> 5, cc = e & 31, col = c0 + cc;
-      const int gi = bi * kStT + r, gj = bj * kStT + r;
-      Ci[r][cc] = (gi < k && col < d) ? C[(int64_t)gi * d + col] : 0.0;
-      Cj[r][cc] = (gj < k && col < d) ? C[(int64_t)gj * d + col] : 0.0;
-    }
-    __syncthreads();
-    const int lim = min(kStC, d - c0);
-    for (int cc = 0; cc < lim; ++cc) {
-      const double a0 = Ci[ty][cc], a1 = Ci[ty + 16][cc];
-      const double b0 = Cj[tx][cc], b1 = Cj[tx + 16][cc];
-      double q = dsub(a0, b0);
-      s00 = dadd(s00, dmul(q, q));
-      q = dsub(a0, b1);
-      s01 = dadd(s01, dmul(q, q));
-      q = dsub(a1, b0);
-      s10 = dadd(s10, dmul(q, q));
-      q = dsub(a1, b1);
-      s11 = dadd(s11, dmul(q, q));
-    }
-  }
-  const double sv[2][2] = {{s00, s01}, {s10, s11}};
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int i = bi * kStT + ty + 16 * a, j = bj * kStT + tx + 16 * b;
-      if (i < k && j < k && j > i) {
-        const double dist = __builtin_sqrt(sv[a][b]);
-        const double v = dmul(dmul(0.25, dist), dist);
-        packed[iut(i, j)] = v;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-        atomicMin(&rmin[ty + 16 * a], bits);
-        atomicMin(&cmin[tx + 16 * b], bits);
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < kStT) {
-    const int i = bi * kStT + threadIdx.x, j = bj * kStT + threadIdx.x;
-    if (i < k && rmin[threadIdx.x] != kInfBits) atomicMin(&dmin[i], rmin[threadIdx.x]);
-    if (j < k && cmin[threadIdx.x] != kInfBits) atomicMin(&dmin[j], cmin[threadIdx.x]);
-  }
+  cyc::kmc::stats_pairs(C, k, d, tps, packed, dmin, blockIdx.x, threadIdx.x);
 }
 
-// diagonal (:69-74): packed(i, i) = min over j != i (+Infinity when every
-// statistic of the row is NaN); k == 1 gives the single NaN of :50.
 __global__ void k_stats_diag(int k, double* __restrict__ packed,
                              const unsigned long long* __restrict__ dmin) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= k) return;
-  if (k == 1) {
-    packed[0] = __builtin_nan("");
-    return;
-  }
-  packed[iut(i, i)] = __longlong_as_double((long long)dmin[i]);
+  cyc::kmc::stats_diag(k, packed, dmin, kInfBits, blockIdx.x, threadIdx.x);
 }
 
 // --------------------------------------------------------------- assign
@@ -1261,16 +1187,7 @@ __global__ void k_nostats_cost_fix(int64_t n, double* __restrict__ cost) {
 __global__ void k_require_norms(const double* __restrict__ C, int k, int d,
                                 const double* __restrict__ xnorm, int64_t n,
                                 unsigned long long* __restrict__ req) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t kd = (int64_t)k * d;
-  for (int64_t i = t0; i < kd; i += stride)
-    if (__builtin_isnan(C[i])) atomicMin(&req[0], (unsigned long long)(i / d));
-  for (int64_t r = t0; r < n; r += stride)
-    if (__builtin_isnan(xnorm[r])) atomicMin(&req[1], (unsigned long long)r);
-  double* out = reinterpret_cast<double*>(req + 2);
-  if (t0 < 2 && t0 < k) out[t0] = seq_norm2(C + t0 * d, d);
-  if (t0 == 2) out[2] = n > 0 ? xnorm[0] : 0.0;
+  cyc::kmc::require_norms(C, k, d, xnorm, n, req, gridDim.x, blockIdx.x, threadIdx.x);
 }
 
 // ------------------------------------------------------- counting sort
@@ -2538,6 +2455,9 @@ int launch_assign(cyc_kmeans_plan p, const double* X, const double* xnorm, int64
   return CYC_OK;
 }
 
+// computeStatistics as three launches (k_center_transpose_fill, k_stats_pairs,
+// k_stats_diag): cyc_kmeans_stats_dev, the silhouette and CYC_KMEANS_PREP=0;
+// a Lloyd call runs the same bodies as jobs of prep_all.
 int do_stats(cyc_kmeans_plan p, const double* C, hipStream_t st) {
   const int k = p->k, d = p->d;
   const int tps = (k + kStT - 1) / kStT;
@@ -2658,8 +2578,12 @@ bool nbrOff() {
 // Moves the bounds to the centers C (the drift against the last call's,
 // then Cp = C) and lists the rows they cannot certify; bd for the screen.
 // The first call of a fit (or after a change of k) screens every row.
-int bounds_prepare(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* C,
-                   const double* xnorm, int64_t n, hipStream_t st, cyc::km8::Bounds& bd) {
+// Three steps: bounds_reserve (buffers; carry: the state of the last call
+// is usable), the center side (k_center_drift, k_drift_top and, inside
+// bounds_filter, k_center_nbrs: separate launches here, jobs of prep_all's
+// three launches in the fused form), bounds_lists (the row side).
+int bounds_reserve(cyc_kmeans_plan p, cyc_kmeans_rows rows, int64_t n, hipStream_t st,
+                   bool& carry) {
   namespace k8 = cyc::km8;
   const int k = p->k, d = p->d;
   int rc;
@@ -2688,11 +2612,17 @@ int bounds_prepare(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* C,
     CYC_HIP(hipMemsetAsync(rows->bCum.ptr, 0, 8, st));
     CYC_HIP(hipMemsetAsync(rows->bRcCum.ptr, 0, 8, st));
   }
-  const bool carry = rows->bValid && rows->bk == k;
+  carry = rows->bValid && rows->bk == k;
   rows->bValid = false;   // until the screen has written the bounds
-  if ((rc = k8::centers_drift(C, (double*)rows->bCp.ptr, k, d, (double*)rows->bDelta.ptr,
-                              (double*)rows->bCcs.ptr, (k8::DriftParams*)rows->bPrm.ptr, st)))
-    return rc;
+  return CYC_OK;
+}
+
+// nbrsReady: the neighbourhoods were built with the centers' preparation
+int bounds_lists(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* xnorm, int64_t n,
+                 hipStream_t st, cyc::km8::Bounds& bd, bool carry, bool nbrsReady) {
+  namespace k8 = cyc::km8;
+  const int k = p->k;
+  int rc;
   bd = k8::Bounds{(float2*)rows->bnd.ptr, nullptr, nullptr};
   bd.lnc = (float*)rows->bLnc.ptr;
   bd.sets = (int32_t*)rows->bSets.ptr;
@@ -2720,7 +2650,7 @@ int bounds_prepare(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* C,
                                 two ? (int32_t*)rows->bTmp2.ptr : nullptr,
                                 two ? (unsigned int*)rows->bCount2.ptr : nullptr,
                                 two ? bd.list : nullptr, two ? bd.listCount : nullptr,
-                                two ? bd.cum : nullptr)))
+                                two ? bd.cum : nullptr, nbrsReady)))
       return rc;
     bd.collected = two;
     if (!nbrOff()) {
@@ -2752,6 +2682,18 @@ int bounds_prepare(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* C,
     rows->bFullRows += n;
   }
   return CYC_OK;
+}
+
+int bounds_prepare(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* C,
+                   const double* xnorm, int64_t n, hipStream_t st, cyc::km8::Bounds& bd) {
+  namespace k8 = cyc::km8;
+  bool carry = false;
+  int rc;
+  if ((rc = bounds_reserve(p, rows, n, st, carry)) ||
+      (rc = k8::centers_drift(C, (double*)rows->bCp.ptr, p->k, p->d, (double*)rows->bDelta.ptr,
+                              (double*)rows->bCcs.ptr, (k8::DriftParams*)rows->bPrm.ptr, st)))
+    return rc;
+  return bounds_lists(p, rows, xnorm, n, st, bd, carry, false);
 }
 
 // The screens' sharded append stage for n rows (with the candidate pass);
@@ -2818,22 +2760,29 @@ int launch_exact(cyc_kmeans_plan p, const double* X, const double* xnorm, int64_
 int do_assign(cyc_kmeans_plan p, const double* X, const double* xnorm, cyc_kmeans_rows rows,
               int64_t n, const double* C, const double* cnorm, int32_t* assign, double* cost,
               int64_t* n_exact_out, hipStream_t st, bool nostats = false,
-              const cyc::km8::Bounds* bd = nullptr, bool approxNorm = false) {
+              const cyc::km8::Bounds* bd = nullptr, bool approxNorm = false,
+              bool prepared = false) {
+  // prepared: prep_all already zeroed the counters and built the center image
   // nostats: findClosest(centers, point) (DistanceMeasure.scala:318-340); the
   // screens certify only rows whose winner both loops return, so only the
   // exact tier differs (no statistics prunes, best starts at +inf)
   const double* statsArg = nostats ? nullptr : (const double*)p->stats.ptr;
   const bool i8 = rows && rows->usable;
   // slowCount (and list3Count for the i8 tier) zeroed by one launch
-  hipLaunchKernelGGL(k_zero2, dim3(1), dim3(64), 0, st, (unsigned int*)p->slowCount.ptr,
-                     i8 ? (unsigned int*)p->list3Count.ptr : nullptr);
-  CYC_LAUNCH_CHECK("k_zero2");
+  if (!prepared) {
+    hipLaunchKernelGGL(k_zero2, dim3(1), dim3(64), 0, st, (unsigned int*)p->slowCount.ptr,
+                       i8 ? (unsigned int*)p->list3Count.ptr : nullptr);
+    CYC_LAUNCH_CHECK("k_zero2");
+  }
   int rc = CYC_OK;
   const int32_t* rowList = nullptr;
   const unsigned int* rowCount = nullptr;
   if (i8) {
     // tier 1: exact-integer i8 screen over every row; undecided rows -> list3
-    if ((rc = cyc::km8::centers_prepare(C, cnorm, p->k, p->d, p->ktp8, p->cb8.ptr,
+    // centers_prepare: k_centers_scan, k_centers_params, k_centers_pack32
+    // (or k_centers_pack), three launches; jobs of prep_all's when prepared
+    if (!prepared &&
+        (rc = cyc::km8::centers_prepare(C, cnorm, p->k, p->d, p->ktp8, p->cb8.ptr,
                                         (float*)p->cq8.ptr, (double*)p->g8.ptr,
                                         (cyc::km8::CenterParams*)p->prm8.ptr,
                                         (double*)p->scr8.ptr, st)))
@@ -2853,7 +2802,7 @@ int do_assign(cyc_kmeans_plan p, const double* X, const double* xnorm, cyc_kmean
                                assign, (int32_t*)p->list3.ptr, (unsigned int*)p->list3Count.ptr,
                                (int32_t*)p->slowList.ptr, (unsigned int*)p->list8Count.ptr, st,
                                useCa ? &ca : nullptr, useRa ? &ra : nullptr,
-                               useSg ? &sg : nullptr, bd)))
+                               useSg ? &sg : nullptr, bd, prepared)))
       return rc;
     rowList = (const int32_t*)p->list3.ptr;
     rowCount = (const unsigned int*)p->list3Count.ptr;
@@ -2921,6 +2870,8 @@ int do_assign(cyc_kmeans_plan p, const double* X, const double* xnorm, cyc_kmean
 // Enqueue k_require_norms and the copy of its result; require_check reads it
 // after the rest of the call is enqueued, so the host waits only for this
 // early, short kernel (its result lands long before the assign finishes).
+// (The separate-launch form: cyc_kmeans_accumulate_dev runs the check as a
+// level-0 job of prep_all, with the same fill before and copy + event after.)
 int require_enqueue(cyc_kmeans_plan p, const double* C, const double* xnorm, int64_t n,
                     hipStream_t st) {
   int rc;
@@ -2937,6 +2888,79 @@ int require_enqueue(cyc_kmeans_plan p, const double* C, const double* xnorm, int
                          hipMemcpyDeviceToHost, st));
   CYC_HIP(hipEventRecord(p->reqEv, st));
   return CYC_OK;
+}
+
+// The fused form of a Lloyd call's center-only work (cyc::km8::
+// centers_prepare_all): what require_enqueue, do_stats, the center side of
+// bounds_prepare, do_assign's k_zero2 and centers_prepare and the screen's
+// k_zero_counters enqueue as twelve launches, as three.  The req buffer
+// holds the 5 req words, padding to 8, then the statistics' k row minima:
+// ONE 0xff byte fill presets req[0..1] and the minima (the pairs job's
+// atomicMin runs beside the transpose job in level 0, so the minima cannot
+// be preset by that job as k_center_transpose_fill does; ~0 is above every
+// statistic's bit pattern and stats_diag reads it as +Infinity).
+// useBnd / carry: bounds_on and bounds_reserve's carry.  statsOnly
+// (cyc_kmeans_stats_dev): the check, the statistics and the transpose alone.
+int prep_all(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* X, const double* xnorm,
+             int64_t n, const double* C, const double* cnorm, bool useBnd, bool carry,
+             hipStream_t st, bool statsOnly = false) {
+  namespace k8 = cyc::km8;
+  const int k = p->k, d = p->d;
+  int rc;
+  const size_t reqBytes = sizeof(unsigned long long) * (8 + (size_t)k);
+  if ((rc = p->req.reserve(reqBytes))) return rc;
+  if (!p->reqHost) CYC_HIP(hipHostMalloc((void**)&p->reqHost, 5 * sizeof(unsigned long long)));
+  if (!p->reqEv) CYC_HIP(hipEventCreateWithFlags(&p->reqEv, hipEventDisableTiming));
+  CYC_HIP(hipMemsetAsync(p->req.ptr, 0xff, reqBytes, st));
+  k8::PrepJobs J;
+  J.C = C;
+  J.cnorm = cnorm;
+  J.k = k;
+  J.d = d;
+  J.stats = (double*)p->stats.ptr;
+  J.dmin = (unsigned long long*)p->req.ptr + 8;
+  J.ct = p->dense_ok ? (double*)p->ct.ptr : nullptr;
+  J.d4 = p->d4;
+  J.kpad = p->kpad;
+  J.xnorm = xnorm;
+  J.n = n;
+  J.req = (unsigned long long*)p->req.ptr;
+  const int64_t work = std::max<int64_t>(n, (int64_t)k * d);
+  J.reqBlocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 2048));
+  if (useBnd) {
+    J.Cp = (double*)rows->bCp.ptr;
+    J.delta = (double*)rows->bDelta.ptr;
+    J.ccs = (double*)rows->bCcs.ptr;
+    J.dprm = (k8::DriftParams*)rows->bPrm.ptr;
+    if (carry && !nbrOff()) {
+      J.nbr = (int32_t*)rows->bNbr.ptr;
+      J.nbrR = (float*)rows->bNbrR.ptr;
+    }
+  }
+  const bool i8 = rows && rows->usable;
+  if (!statsOnly) {
+    J.zeroA = (unsigned int*)p->slowCount.ptr;
+    J.zeroB = i8 ? (unsigned int*)p->list3Count.ptr : nullptr;
+  }
+  if (i8 && !statsOnly) {
+    J.ktp = p->ktp8;
+    J.Cb = p->cb8.ptr;
+    J.cq = (float*)p->cq8.ptr;
+    J.g = (double*)p->g8.ptr;
+    J.cprm = (k8::CenterParams*)p->prm8.ptr;
+    J.scratch = (double*)p->scr8.ptr;
+    // the screen's counters, for the arguments do_assign will pass it
+    k8::CandArgs ca;
+    k8::RefineArgs ra;
+    k8::AppendStage sg;
+    bool useCa = false, useRa = false, useSg = false;
+    if ((rc = cand_args(p, n, X, nullptr, C, cnorm, false, ca, useCa)) ||
+        (rc = refine_args(p, n, useCa, ra, useRa)) || (rc = stage_args(p, n, useCa, sg, useSg)))
+      return rc;
+    J.zero = k8::screen_zero_args((unsigned int*)p->list8Count.ptr, useCa ? &ca : nullptr,
+                                  useRa ? &ra : nullptr, useSg ? &sg : nullptr);
+  }
+  return k8::centers_prepare_all(J, st, p->reqHost, p->reqEv);
 }
 
 // The IllegalArgumentException the reference raises first, if any:
@@ -3449,6 +3473,9 @@ int cyc_kmeans_stats_dev(cyc_kmeans_plan p, const double* C, double* stats_out, 
     if ((rc = cos_enqueue(p, cn, p->k >= 2, nullptr, 0, st))) return rc;
     if (p->dense_ok && (rc = cos_transpose(p, C, st))) return rc;
     if ((rc = cos_stats(p, C, cn, st))) return rc;
+  } else if (cyc::km8::prep_fused()) {
+    if ((rc = prep_all(p, nullptr, nullptr, nullptr, 0, C, nullptr, false, false, st, true)))
+      return rc;
   } else {
     if ((rc = require_enqueue(p, C, nullptr, 0, st))) return rc;
     if ((rc = do_stats(p, C, st))) return rc;
@@ -3700,15 +3727,30 @@ int cyc_kmeans_accumulate_dev(cyc_kmeans_plan p, const double* X, const double* 
         (rc = cos_assign(p, X, xnorm, rows, n, C, cnorm, assign, nullptr, nullptr, st, false)))
       return rc;
   } else {
-    if ((rc = require_enqueue(p, C, xnorm, n, st))) return rc;
-    if ((rc = do_stats(p, C, st))) return rc;
+    // the center-only work in three launches (prep_all), or as the separate
+    // launches (CYC_KMEANS_PREP=0; an image of d > 256, whose screen packs
+    // another center image)
+    const bool fused = cyc::km8::prep_fused() &&
+                       (!(rows && rows->usable) || cyc::km8::uses32(d));
     cyc::km8::Bounds bd{};
-    if (useBnd) {
-      if ((rc = bounds_prepare(p, rows, C, xnorm, n, st, bd))) return rc;
-      assign = (int32_t*)rows->bAssign.ptr;
+    if (fused) {
+      bool carry = false;
+      if (useBnd && (rc = bounds_reserve(p, rows, n, st, carry))) return rc;
+      if ((rc = prep_all(p, rows, X, xnorm, n, C, cnorm, useBnd, carry, st))) return rc;
+      if (useBnd) {
+        if ((rc = bounds_lists(p, rows, xnorm, n, st, bd, carry, true))) return rc;
+        assign = (int32_t*)rows->bAssign.ptr;
+      }
+    } else {
+      if ((rc = require_enqueue(p, C, xnorm, n, st))) return rc;
+      if ((rc = do_stats(p, C, st))) return rc;
+      if (useBnd) {
+        if ((rc = bounds_prepare(p, rows, C, xnorm, n, st, bd))) return rc;
+        assign = (int32_t*)rows->bAssign.ptr;
+      }
     }
     if ((rc = do_assign(p, X, xnorm, rows, n, C, cnorm, assign, nullptr, nullptr, st, false,
-                        useBnd ? &bd : nullptr, approxNorm)))
+                        useBnd ? &bd : nullptr, approxNorm, fused)))
       return rc;
     if (useBnd) {
       rows->bValid = true;

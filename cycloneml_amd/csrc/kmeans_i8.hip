@@ -386,11 +386,15 @@ __global__ __launch_bounds__(256) void k_rows_quantize(const double* __restrict_
 }
 
 // One wave per center: max |c_j|, |c|_1, finiteness.
-__global__ __launch_bounds__(256) void k_centers_scan(const double* __restrict__ C, int k, int d,
-                                                      double* __restrict__ cmax,
-                                                      double* __restrict__ cn1) {
-  const int lane = threadIdx.x & 63;
-  const int c = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+// (the d_* functions are the kernels' bodies, shared with the fused levels
+// of centers_prepare_all; bid / tid: the stand-alone launch's block and
+// thread index)
+__device__ __forceinline__ void d_centers_scan(const double* __restrict__ C, int k, int d,
+                                               double* __restrict__ cmax,
+                                               double* __restrict__ cn1, unsigned bid,
+                                               unsigned tid) {
+  const int lane = tid & 63;
+  const int c = (int)((bid * 256 + tid) >> 6);
   if (c >= k) return;
   double m = 0.0, s1 = 0.0;
   bool fin = true;
@@ -408,29 +412,34 @@ __global__ __launch_bounds__(256) void k_centers_scan(const double* __restrict__
     cn1[c] = s1 * (1.0 + 0x1p-40);
   }
 }
+__global__ __launch_bounds__(256) void k_centers_scan(const double* __restrict__ C, int k, int d,
+                                                      double* __restrict__ cmax,
+                                                      double* __restrict__ cn1) {
+  d_centers_scan(C, k, d, cmax, cn1, blockIdx.x, threadIdx.x);
+}
 
 // Single block: the launch's exponent, balance and on/off flag.
-__global__ __launch_bounds__(256) void k_centers_params(int k, const double* __restrict__ cmax,
-                                                        const double* __restrict__ cn1,
-                                                        CenterParams* __restrict__ prm) {
+__device__ __forceinline__ void d_centers_params(int k, const double* __restrict__ cmax,
+                                                 const double* __restrict__ cn1,
+                                                 CenterParams* __restrict__ prm, unsigned tid) {
   __shared__ double sm[256], sn[256];
   double m = 0.0, nmax = 0.0;
-  for (int c = threadIdx.x; c < k; c += 256) {
+  for (int c = tid; c < k; c += 256) {
     m = __builtin_fmax(m, cmax[c]);
     nmax = __builtin_fmax(nmax, cn1[c]);
     if (!(cmax[c] <= 0x1p60)) m = __builtin_inf();   // non-finite center
   }
-  sm[threadIdx.x] = m;
-  sn[threadIdx.x] = nmax;
+  sm[tid] = m;
+  sn[tid] = nmax;
   __syncthreads();
   for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      sm[threadIdx.x] = __builtin_fmax(sm[threadIdx.x], sm[threadIdx.x + off]);
-      sn[threadIdx.x] = __builtin_fmax(sn[threadIdx.x], sn[threadIdx.x + off]);
+    if (tid < (unsigned)off) {
+      sm[tid] = __builtin_fmax(sm[tid], sm[tid + off]);
+      sn[tid] = __builtin_fmax(sn[tid], sn[tid + off]);
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
+  if (tid == 0) {
     const double gm = sm[0];
     const int ec = choose_exp(__builtin_isfinite(gm) ? gm : 0.0);
     CenterParams p;
@@ -442,6 +451,11 @@ __global__ __launch_bounds__(256) void k_centers_params(int k, const double* __r
     p.k = k;
     *prm = p;
   }
+}
+__global__ __launch_bounds__(256) void k_centers_params(int k, const double* __restrict__ cmax,
+                                                        const double* __restrict__ cn1,
+                                                        CenterParams* __restrict__ prm) {
+  d_centers_params(k, cmax, cn1, prm, threadIdx.x);
 }
 
 // Packed B fragments of v_mfma_i32_16x16x64_i8: lane l of 16-center tile ct,
@@ -745,13 +759,14 @@ __global__ __launch_bounds__(256, KS <= 4 ? 3 : 2) void k_screen(
 
 __device__ __forceinline__ double err_term2(int e, double n1, double mu, int d);
 __device__ __forceinline__ double err_term1(int e, double n1, double mu);
-__global__ __launch_bounds__(256) void k_centers_pack32(
+__device__ __forceinline__ void d_centers_pack32(
     const double* __restrict__ C, const double* __restrict__ cnorm, int k, int d, int S, int ktp,
     const double* __restrict__ cn1, const CenterParams* __restrict__ prm, uint4* __restrict__ Cb,
     float* __restrict__ cq, double* __restrict__ g, float* __restrict__ cq2,
-    double* __restrict__ g2, float* __restrict__ cq1, double* __restrict__ g1) {
+    double* __restrict__ g2, float* __restrict__ cq1, double* __restrict__ g1, unsigned bid,
+    unsigned tid) {
   const CenterParams p = *prm;
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t idx = (int64_t)bid * 256 + tid;
   const int64_t total = (int64_t)ktp * S * 64;
   if (idx < total) {
     const int lane = (int)(idx & 63);
@@ -801,6 +816,14 @@ __global__ __launch_bounds__(256) void k_centers_pack32(
       cq2[c] = cq1[c] = 0x1.fffffep127f;
     }
   }
+}
+__global__ __launch_bounds__(256) void k_centers_pack32(
+    const double* __restrict__ C, const double* __restrict__ cnorm, int k, int d, int S, int ktp,
+    const double* __restrict__ cn1, const CenterParams* __restrict__ prm, uint4* __restrict__ Cb,
+    float* __restrict__ cq, double* __restrict__ g, float* __restrict__ cq2,
+    double* __restrict__ g2, float* __restrict__ cq1, double* __restrict__ g1) {
+  d_centers_pack32(C, cnorm, k, d, S, ktp, cn1, prm, Cb, cq, g, cq2, g2, cq1, g1, blockIdx.x,
+                   threadIdx.x);
 }
 
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -2635,15 +2658,13 @@ int compact(unsigned int* counts, unsigned int cap, const int32_t* src, int32_t*
 // set get exact fp64 distances to those candidates (k_screen_cands), the
 // others the three-limb pass.  With `stg` (and ca) every 32x32 kernel
 // appends through its shards, compacted after each launch.
-// Up to 8 counter ranges zeroed in one launch (a block per range).
-struct ZeroArgs {
-  unsigned int* p[8];
-  int w[8];
-  int n;
-};
+// Up to 8 counter ranges zeroed in one launch (a block per range; ZeroArgs).
+__device__ __forceinline__ void d_zero_counters(const ZeroArgs& z, unsigned bid, unsigned tid) {
+  unsigned int* q = z.p[bid];
+  for (int i = (int)tid; i < z.w[bid]; i += 256) q[i] = 0u;
+}
 __global__ __launch_bounds__(256) void k_zero_counters(ZeroArgs z) {
-  unsigned int* q = z.p[blockIdx.x];
-  for (int i = threadIdx.x; i < z.w[blockIdx.x]; i += 256) q[i] = 0u;
+  d_zero_counters(z, blockIdx.x, threadIdx.x);
 }
 
 template <int S, int W>
@@ -2652,28 +2673,13 @@ int screen32(const void* img, const int2* meta, const double* xnorm, int64_t n, 
              const CenterParams* prm, int ktp, int32_t* assign, int32_t* list,
              unsigned int* listCount, int32_t* list2, unsigned int* list2Count,
              const CandArgs* ca, hipStream_t st, const RefineArgs* ra = nullptr,
-             const AppendStage* stg = nullptr, const Bounds* bd = nullptr) {
+             const AppendStage* stg = nullptr, const Bounds* bd = nullptr,
+             bool countersZeroed = false) {
   const AppendStage* sg = ca ? stg : nullptr;
   const unsigned scap = sg ? sg->cap : 0u;
-  {
+  if (!countersZeroed) {
     // every counter of the pass zeroed by one launch (six fills before)
-    ZeroArgs z{};
-    auto add = [&](unsigned int* q, int words) {
-      if (q) {
-        z.p[z.n] = q;
-        z.w[z.n++] = words;
-      }
-    };
-    add(list2Count, 1);
-    if (ca) {
-      add(ca->candCount, 1);
-      add(ca->candCount2, 1);
-    }
-    if (ra && ca) {
-      add(ra->cand1Count, 1);
-      add(ra->fullCount, 2);
-    }
-    add(sg ? sg->counts : nullptr, kSets * kShards * kShardStride);
+    const ZeroArgs z = screen_zero_args(list2Count, ca, ra, stg);
     if (z.n) {
       hipLaunchKernelGGL(k_zero_counters, dim3(z.n), dim3(256), 0, st, z);
       CYC_LAUNCH_CHECK("k_zero_counters");
@@ -2880,12 +2886,13 @@ int screen32(const void* img, const int2* meta, const double* xnorm, int64_t n, 
 // One wave per center: the drift |C_c - Cp_c| and |C_c|^2, both rounded up
 // (fp64 sums of d <= 256 squares: relative error < (d + 2) 2^-53 < 2^-44),
 // then Cp_c = C_c.
-__global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__ C,
-                                                      double* __restrict__ Cp, int k, int d,
-                                                      double* __restrict__ delta,
-                                                      double* __restrict__ ccs) {
-  const int lane = threadIdx.x & 63;
-  const int c = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+__device__ __forceinline__ void d_center_drift(const double* __restrict__ C,
+                                               double* __restrict__ Cp, int k, int d,
+                                               double* __restrict__ delta,
+                                               double* __restrict__ ccs, unsigned bid,
+                                               unsigned tid) {
+  const int lane = tid & 63;
+  const int c = (int)((bid * 256 + tid) >> 6);
   if (c >= k) return;
   double s = 0.0, q = 0.0;
   for (int j = lane; j < d; j += 64) {
@@ -2902,15 +2909,21 @@ __global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__
     ccs[c] = q * (1.0 + 0x1p-40);
   }
 }
+__global__ __launch_bounds__(256) void k_center_drift(const double* __restrict__ C,
+                                                      double* __restrict__ Cp, int k, int d,
+                                                      double* __restrict__ delta,
+                                                      double* __restrict__ ccs) {
+  d_center_drift(C, Cp, k, d, delta, ccs, blockIdx.x, threadIdx.x);
+}
 
 // Single block: the two largest drifts (and the largest one's center) and
 // max |c|^2; any non-finite drift or norm sets `bad`.
-__global__ __launch_bounds__(1024) void k_drift_top(const double* __restrict__ delta,
-                                                    const double* __restrict__ ccs, int k,
-                                                    DriftParams* __restrict__ prm) {
+__device__ __forceinline__ void d_drift_top(const double* __restrict__ delta,
+                                            const double* __restrict__ ccs, int k,
+                                            DriftParams* __restrict__ prm, unsigned tid) {
   __shared__ double s1[1024], s2[1024], sc[1024];
   __shared__ int si[1024];
-  const int t = threadIdx.x;
+  const int t = (int)tid;
   double d1 = 0.0, d2 = 0.0, cm = 0.0;
   int i1 = -1;
   bool bad = false;
@@ -2956,6 +2969,11 @@ __global__ __launch_bounds__(1024) void k_drift_top(const double* __restrict__ d
     *prm = p;
   }
 }
+__global__ __launch_bounds__(1024) void k_drift_top(const double* __restrict__ delta,
+                                                    const double* __restrict__ ccs, int k,
+                                                    DriftParams* __restrict__ prm) {
+  d_drift_top(delta, ccs, k, prm, threadIdx.x);
+}
 
 // The listed rows of a kBndRows-row block in row order: tmp[block *
 // kBndRows ...], their count in bcount[block] (masks: the wave's ballot of
@@ -2989,10 +3007,10 @@ __device__ __forceinline__ void bnd_block_list(const unsigned long long (&masks)
 // a and its kCandMax - 1 nearest other centers (-1 padding when k is
 // smaller), nbrR[a] = a lower bound of the distance from c_a to every
 // other center (the next nearest; +inf when none is left).
-__global__ __launch_bounds__(64) void k_center_nbrs(const double* __restrict__ stats, int k,
-                                                    int32_t* __restrict__ nbr,
-                                                    float* __restrict__ nbrR) {
-  const int a = blockIdx.x, lane = threadIdx.x;
+// (a: the wave's center, lane: the thread's lane in it)
+__device__ __forceinline__ void d_center_nbrs(const double* __restrict__ stats, int k,
+                                              int32_t* __restrict__ nbr,
+                                              float* __restrict__ nbrR, int a, int lane) {
   constexpr int T = kCandMax;   // kCandMax - 1 members + the next one
   double v[T];
   int ix[T];
@@ -3056,6 +3074,11 @@ __global__ __launch_bounds__(64) void k_center_nbrs(const double* __restrict__ s
       }
     }
   }
+}
+__global__ __launch_bounds__(64) void k_center_nbrs(const double* __restrict__ stats, int k,
+                                                    int32_t* __restrict__ nbr,
+                                                    float* __restrict__ nbrR) {
+  d_center_nbrs(stats, k, nbr, nbrR, blockIdx.x, threadIdx.x);
 }
 
 // kBndRows rows per workgroup (8 per thread, coalesced): a row keeps its
@@ -3238,6 +3261,93 @@ int launch_screen(const void* img, const int2* meta, const double* xnorm, int64_
   return CYC_OK;
 }
 
+// ---------------------------------------------------------------------------
+// centers_prepare_all (kmeans_i8.hpp PrepJobs): the center-only kernels of a
+// Lloyd call as jobs of three launches, one per dependency level.
+// blockIdx.y picks the job, blockIdx.x is the block index the job's
+// stand-alone kernel has; a block at or past its job's extent (ext[job], 0
+// for an absent job) exits.  Every job runs the stand-alone kernel's body
+// with that kernel's block and thread indices, so each output is bitwise what
+// the separate launches write.  No job uses dynamic LDS.
+struct PrepLevel {
+  unsigned ext[8];   // blocks per job
+  int tps;           // statistics tiles per side
+  int S, ktp32;      // center image: 32-dim substeps, 32-center tiles
+};
+enum { kP0Pairs, kP0Require, kP0Drift, kP0Scan, kP0Transpose, kP0Zero2, kP0Zero, kP0Jobs };
+enum { kP1DriftTop, kP1Params, kP1Diag, kP1Jobs };
+enum { kP2Pack, kP2Nbrs, kP2Jobs };
+
+// Level 0: reads C, Cp (drift only, which also writes it: no other job may
+// read Cp), xnorm.  Every job is a 256-thread kernel as launched alone,
+// except the two-word zeroing (64 threads alone; only threads 0 and 1 act,
+// so the surplus is idle).  The longest job (the pairs) is dispatched first.
+__global__ __launch_bounds__(256) void k_prep_level0(PrepJobs J, PrepLevel L) {
+  const unsigned job = blockIdx.y, bid = blockIdx.x, tid = threadIdx.x;
+  if (bid >= L.ext[job]) return;
+  switch (job) {
+    case kP0Pairs:
+      kmc::stats_pairs(J.C, J.k, J.d, L.tps, J.stats, J.dmin, bid, tid);
+      break;
+    case kP0Require:
+      kmc::require_norms(J.C, J.k, J.d, J.xnorm, J.n, J.req, L.ext[kP0Require], bid, tid);
+      break;
+    case kP0Drift:
+      d_center_drift(J.C, J.Cp, J.k, J.d, J.delta, J.ccs, bid, tid);
+      break;
+    case kP0Scan:
+      d_centers_scan(J.C, J.k, J.d, J.scratch, J.scratch + J.k, bid, tid);
+      break;
+    case kP0Transpose:
+      kmc::center_transpose_fill(J.C, J.k, J.d, J.d4, J.kpad, J.ct, nullptr, 0ull, bid, tid);
+      break;
+    case kP0Zero2:
+      kmc::zero2(J.zeroA, J.zeroB, tid);
+      break;
+    default:
+      d_zero_counters(J.zero, bid, tid);
+      break;
+  }
+}
+
+// Level 1: the single-block reductions of level 0's per-center scalars and
+// the statistics' diagonal.  Launched at 1024 threads (k_drift_top's block);
+// the 256-thread jobs are MASKED: waves 4..15 skip the body and end, so the
+// body's barriers and its reduction tree see exactly the 256 threads of the
+// stand-alone launch (a barrier waits only for the waves still alive).
+__global__ __launch_bounds__(1024) void k_prep_level1(PrepJobs J, PrepLevel L) {
+  const unsigned job = blockIdx.y, bid = blockIdx.x, tid = threadIdx.x;
+  if (bid >= L.ext[job]) return;
+  switch (job) {
+    case kP1DriftTop:
+      d_drift_top(J.delta, J.ccs, J.k, J.dprm, tid);
+      break;
+    case kP1Params:
+      if (tid < 256) d_centers_params(J.k, J.scratch, J.scratch + J.k, J.cprm, tid);
+      break;
+    default:   // dmin was preset by a 0xff byte fill: ~0 marks an empty row
+      if (tid < 256) kmc::stats_diag(J.k, J.stats, J.dmin, ~0ull, bid, tid);
+      break;
+  }
+}
+
+// Level 2: the center image (needs prm and cn1) at its own 256-thread
+// tiling; the neighbourhoods (need the finished statistics) RE-TILED: one
+// wave per center as alone, four centers per block instead of one (no
+// barrier or LDS in the body: a wave's work and order are unchanged).
+__global__ __launch_bounds__(256) void k_prep_level2(PrepJobs J, PrepLevel L) {
+  const unsigned job = blockIdx.y, bid = blockIdx.x, tid = threadIdx.x;
+  if (bid >= L.ext[job]) return;
+  if (job == kP2Pack) {
+    const size_t t16 = (size_t)J.ktp * 16;
+    d_centers_pack32(J.C, J.cnorm, J.k, J.d, L.S, L.ktp32, J.scratch + J.k, J.cprm, (uint4*)J.Cb,
+                     J.cq, J.g, J.cq + t16, J.g + t16, J.cq + 2 * t16, J.g + 2 * t16, bid, tid);
+  } else {
+    const int a = (int)(bid * 4 + (tid >> 6));
+    if (a < J.k) d_center_nbrs(J.stats, J.k, J.nbr, J.nbrR, a, (int)(tid & 63));
+  }
+}
+
 }  // namespace
 
 int rows_quantize(const double* X, int64_t n, int d, void* img, int2* meta, hipStream_t st,
@@ -3267,6 +3377,10 @@ int rows_quantize(const double* X, int64_t n, int d, void* img, int2* meta, hipS
   return CYC_OK;
 }
 
+// The center image as three dependent launches (scan, params, pack): the
+// cosine plan, cyc_kmeans_assign_dev / point_cost_dev, d > 256 and
+// CYC_KMEANS_PREP=0.  A Euclidean Lloyd call runs the same three bodies as
+// jobs of centers_prepare_all's levels 0, 1 and 2.
 int centers_prepare(const double* C, const double* cnorm, int k, int d, int ktp, void* Cb,
                     float* cq, double* g, CenterParams* prm, double* scratch, hipStream_t st) {
   const int KS = ksteps(d);
@@ -3298,6 +3412,92 @@ int centers_prepare(const double* C, const double* cnorm, int k, int d, int ktp,
   return CYC_OK;
 }
 
+ZeroArgs screen_zero_args(unsigned int* list2Count, const CandArgs* ca, const RefineArgs* ra,
+                          const AppendStage* stg) {
+  const AppendStage* sg = ca ? stg : nullptr;
+  ZeroArgs z{};
+  auto add = [&](unsigned int* q, int words) {
+    if (q) {
+      z.p[z.n] = q;
+      z.w[z.n++] = words;
+    }
+  };
+  add(list2Count, 1);
+  if (ca) {
+    add(ca->candCount, 1);
+    add(ca->candCount2, 1);
+  }
+  if (ra && ca) {
+    add(ra->cand1Count, 1);
+    add(ra->fullCount, 2);
+  }
+  add(sg ? sg->counts : nullptr, kSets * kShards * kShardStride);
+  return z;
+}
+
+bool prep_fused() {
+  static const bool on = [] {
+    const char* e = std::getenv("CYC_KMEANS_PREP");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// The center-only work of a Lloyd call in three launches (kmeans_i8.hpp
+// PrepJobs; the kernels above).  The require check's result is copied to the
+// host right after level 0, so require_check's wait ends long before the
+// row-side kernels do.
+int centers_prepare_all(const PrepJobs& J, hipStream_t st, void* reqHost, hipEvent_t reqEv) {
+  const int k = J.k, d = J.d;
+  if (J.Cb && !uses32(d)) {
+    set_error("centers_prepare_all packs the 32x32 screen's image only (d <= 256)");
+    return CYC_ERR_INVALID_ARG;
+  }
+  if (J.nbr && !J.stats) {
+    set_error("centers_prepare_all: neighbourhoods need the statistics");
+    return CYC_ERR_INVALID_ARG;
+  }
+  auto launch = [&](auto kern, const PrepLevel& L, int jobs, unsigned threads) {
+    unsigned gx = 0;
+    for (int i = 0; i < jobs; ++i) gx = std::max(gx, L.ext[i]);
+    if (gx) hipLaunchKernelGGL(kern, dim3(gx, (unsigned)jobs), dim3(threads), 0, st, J, L);
+  };
+  PrepLevel L0{};
+  L0.tps = (k + kmc::kStT - 1) / kmc::kStT;
+  L0.ext[kP0Pairs] = J.stats && k >= 2 ? (unsigned)(L0.tps * (L0.tps + 1) / 2) : 0u;
+  L0.ext[kP0Require] = J.req ? J.reqBlocks : 0u;
+  L0.ext[kP0Drift] = J.Cp ? (unsigned)((k + 3) / 4) : 0u;
+  L0.ext[kP0Scan] = J.Cb ? (unsigned)((k + 3) / 4) : 0u;
+  L0.ext[kP0Transpose] = J.ct ? (unsigned)(((int64_t)J.d4 * J.kpad + 255) / 256) : 0u;
+  L0.ext[kP0Zero2] = J.zeroA ? 1u : 0u;
+  L0.ext[kP0Zero] = (unsigned)J.zero.n;
+  launch(k_prep_level0, L0, kP0Jobs, 256);
+  CYC_LAUNCH_CHECK("k_prep_level0");
+  if (J.req) {
+    CYC_HIP(hipMemcpyAsync(reqHost, J.req, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           st));
+    CYC_HIP(hipEventRecord(reqEv, st));
+  }
+  PrepLevel L1{};
+  L1.ext[kP1DriftTop] = J.Cp ? 1u : 0u;
+  L1.ext[kP1Params] = J.Cb ? 1u : 0u;
+  L1.ext[kP1Diag] = J.stats ? (unsigned)((k + 255) / 256) : 0u;
+  launch(k_prep_level1, L1, kP1Jobs, 1024);
+  CYC_LAUNCH_CHECK("k_prep_level1");
+  PrepLevel L2{};
+  if (J.Cb) {
+    L2.S = 2 * ksteps(d);
+    L2.ktp32 = tiles32(k);
+    const int64_t total =
+        std::max<int64_t>((int64_t)L2.ktp32 * L2.S * 64, (int64_t)L2.ktp32 * 32);
+    L2.ext[kP2Pack] = (unsigned)((total + 255) / 256);
+  }
+  L2.ext[kP2Nbrs] = J.nbr ? (unsigned)((k + 3) / 4) : 0u;
+  launch(k_prep_level2, L2, kP2Jobs, 256);
+  CYC_LAUNCH_CHECK("k_prep_level2");
+  return CYC_OK;
+}
+
 int centers_drift(const double* C, double* Cp, int k, int d, double* delta, double* ccs,
                   DriftParams* prm, hipStream_t st) {
   hipLaunchKernelGGL(k_center_drift, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, C, Cp, k, d,
@@ -3315,12 +3515,12 @@ int bounds_filter(const int32_t* assign, float2* ub_lb, float* lnc, unsigned cha
                   unsigned int* rcCount, unsigned long long* rcCum, const double* stats,
                   int32_t* nbr, float* nbrR, hipStream_t st, int32_t* tmp2,
                   unsigned int* bcount2, int32_t* list1, unsigned int* list1Count,
-                  unsigned long long* cum1) {
+                  unsigned long long* cum1, bool nbrsReady) {
   const int64_t nb = bounds_blocks(n);
   const bool two = tmp2 && bcount2 && list1 && list1Count;
   if (nb <= 0) return CYC_OK;
   KernelTimer timer("k_kmeans_bounds", st);
-  if (stats) {
+  if (stats && !nbrsReady) {
     hipLaunchKernelGGL(k_center_nbrs, dim3((unsigned)k), dim3(64), 0, st, stats, k, nbr, nbrR);
     CYC_LAUNCH_CHECK("k_center_nbrs");
   }
@@ -3372,7 +3572,7 @@ int screen(const void* img, const int2* meta, const double* xnorm, int64_t n, in
            const CenterParams* prm, int ktp, int32_t* assign, int32_t* list,
            unsigned int* listCount, int32_t* list2, unsigned int* list2Count, hipStream_t st,
            const CandArgs* ca, const RefineArgs* ra, const AppendStage* stg,
-           const Bounds* bd) {
+           const Bounds* bd, bool countersZeroed) {
   if (n <= 0) return CYC_OK;
   if (stg && stg->cap < shard_cap(n)) {
     set_error("append stage smaller than shard_cap(n)");
@@ -3385,8 +3585,8 @@ int screen(const void* img, const int2* meta, const double* xnorm, int64_t n, in
   if (uses32(d)) {
     const int k32 = ktp * 16 / 32;   // launch over the padded center range (cq = +inf)
     switch (ksteps(d)) {
-      case 2: return screen32<4, 4>(img, meta, xnorm, n, d, Cb, cq, g, cnorm, prm, k32, assign, list, listCount, list2, list2Count, ca, st, ra, stg, bd);
-      default: return screen32<8, 4>(img, meta, xnorm, n, d, Cb, cq, g, cnorm, prm, k32, assign, list, listCount, list2, list2Count, ca, st, ra, stg, bd);
+      case 2: return screen32<4, 4>(img, meta, xnorm, n, d, Cb, cq, g, cnorm, prm, k32, assign, list, listCount, list2, list2Count, ca, st, ra, stg, bd, countersZeroed);
+      default: return screen32<8, 4>(img, meta, xnorm, n, d, Cb, cq, g, cnorm, prm, k32, assign, list, listCount, list2, list2Count, ca, st, ra, stg, bd, countersZeroed);
     }
   }
   switch (ksteps(d)) {
