@@ -7,3 +7,10 @@ include/cyclone.h); these modules mirror the reference's Scala interfaces.
 __version__ = "0.1.0"
 
 from . import _native  # noqa: F401  (loads nothing until first use)
+from .regression import (  # noqa: F401
+    LinearRegression,
+    LinearRegressionModel,
+    SingularMatrixException,
+    WeightedLeastSquares,
+    WeightedLeastSquaresModel,
+)

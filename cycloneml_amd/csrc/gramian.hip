@@ -157,6 +157,130 @@ __global__ __launch_bounds__(GT, 2) void k_gram_tiles(
       }
 }
 
+// WeightedLeastSquares.Aggregator.add (ml/optim/WeightedLeastSquares.scala)
+// as one weighted syrk: the staged tiles of k_gram_tiles over the augmented
+// row z_r = [a_r, b_r, 1.0] of width q = p + 2, U += sum_r w_r z_r z_r^T.
+// The packed result holds every aggregator field: aaSum (leading p x p),
+// abSum (column p), bbSum (p, p), aSum (column p + 1), bSum (p, p + 1), wSum
+// (p + 1, p + 1).  The i-side panel is scaled by w_r as it is staged (one
+// dmul per element: spr's alpha x_i), the j-side panel is staged as it is.
+// A row of weight 0 stages zeros in both panels without reading its
+// features (the reference's `if (w > 0.0)`: NaN or Inf features of such a
+// row never reach an accumulator).  A negative or NaN weight raises *flag
+// (the row stages zeros; the host fails the call).  tilesPerSide, the slab
+// layout and k_gram_fold are k_gram_tiles' with q for p.
+__global__ __launch_bounds__(GT, 2) void k_wls_tiles(
+    const double* __restrict__ X, int64_t nrows, int p, const double* __restrict__ y,
+    const double* __restrict__ w, int tilesPerSide, int64_t rowsPerSplit,
+    double* __restrict__ slab, int* __restrict__ flag) {
+  __shared__ __attribute__((aligned(16))) double Ai[KC * LDSW];
+  __shared__ __attribute__((aligned(16))) double Aj[KC * LDSW];
+  int t = blockIdx.x, ti = 0;
+  while (t >= tilesPerSide - ti) { t -= tilesPerSide - ti; ++ti; }
+  const int tj = ti + t;
+  const int I0 = ti * TILE, J0 = tj * TILE;
+  const int64_t r0 = (int64_t)blockIdx.y * rowsPerSplit;
+  const int64_t r1 = min<int64_t>(nrows, r0 + rowsPerSplit);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wy = wave >> 1, wx = wave & 1;
+
+  cyc_double4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = cyc_double4{0.0, 0.0, 0.0, 0.0};
+
+  // the staging map of k_gram_tiles: thread -> row sr, cols sc .. sc + 7
+  const int sr = tid >> 4, sc = (tid & 15) * 8;
+  double ri[8], rj[8];
+  auto load_panel = [&](const double* rowp, double yr, int c0, double* dst) {
+    if ((p & 1) == 0 && c0 + 8 <= p) {
+      const double2* v = reinterpret_cast<const double2*>(rowp + c0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        double2 t2 = v[e];
+        dst[2 * e] = t2.x;
+        dst[2 * e + 1] = t2.y;
+      }
+    } else {
+      // ragged panels, odd p and the augmented columns: label, then ones
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = c0 + e;
+        double v = 0.0;
+        if (c < p) v = rowp[c];
+        else if (c == p) v = yr;
+        else if (c == p + 1) v = 1.0;
+        dst[e] = v;
+      }
+    }
+  };
+  auto load = [&](int64_t rb) {
+    const int64_t r = rb + sr;
+    double wr = 0.0;
+    if (r < r1) {
+      wr = w ? w[r] : 1.0;
+      // once per row: the first tile pair's first staging thread of the row
+      if (!(wr >= 0.0) && blockIdx.x == 0 && (tid & 15) == 0) atomicOr(flag, 1);
+    }
+    if (wr > 0.0) {
+      const double* rowp = X + r * p;
+      const double yr = y[r];
+      load_panel(rowp, yr, I0 + sc, ri);
+      load_panel(rowp, yr, J0 + sc, rj);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ri[e] = dmul(wr, ri[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ri[e] = rj[e] = 0.0;
+    }
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      Ai[sr * LDSW + sc + e] = ri[e];
+      Aj[sr * LDSW + sc + e] = rj[e];
+    }
+  };
+
+  if (r0 < r1) load(r0);
+  for (int64_t rb = r0; rb < r1; rb += KC) {
+    __syncthreads();
+    store();
+    __syncthreads();
+    if (rb + KC < r1) load(rb + KC);
+#pragma unroll
+    for (int kk = 0; kk < KC; kk += 4) {
+      double a[4], b[4];
+      const int krow = kk + (lane >> 4);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        a[q] = Ai[krow * LDSW + wy * 64 + q * 16 + (lane & 15)];
+        b[q] = Aj[krow * LDSW + wx * 64 + q * 16 + (lane & 15)];
+      }
+#pragma unroll
+      for (int qa = 0; qa < 4; ++qa)
+#pragma unroll
+        for (int qb = 0; qb < 4; ++qb)
+          acc[qa][qb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[qa], b[qb], acc[qa][qb], 0, 0, 0);
+    }
+  }
+
+  const int pairs = tilesPerSide * (tilesPerSide + 1) / 2;
+  double* out = slab + ((size_t)blockIdx.y * pairs + blockIdx.x) * TILE * TILE;
+#pragma unroll
+  for (int qa = 0; qa < 4; ++qa)
+#pragma unroll
+    for (int qb = 0; qb < 4; ++qb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = wy * 64 + qa * 16 + (lane >> 4) + 4 * r;
+        const int j = wx * 64 + qb * 16 + (lane & 15);
+        out[i * TILE + j] = acc[qa][qb][r];
+      }
+}
+
 // The same tiles with the panels DMA'd from HBM straight into LDS
 // (buffer_load ... lds, one 1 KiB row of a panel per wave instruction: no
 // staging registers, no ds_write) into NB = 2 chunk buffers: the next
@@ -550,22 +674,37 @@ struct cyc_gramian_plan_s {
   cyc::DeviceBuffer sumSlab;  // k_gram_dma<..., SUMS> column-sum partials
 };
 
+// The weighted syrk of width numFeatures + 2 (k_wls_tiles): its split-K slab,
+// the densified CSR chunk and the bad-weight flag.
+struct cyc_wls_plan_s {
+  int p = 0;   // numFeatures
+  std::mutex mu;
+  cyc::DeviceBuffer slab;
+  cyc::DeviceBuffer chunk;
+  cyc::DeviceBuffer flag;
+  int64_t lastSplits = 0;
+};
+
 namespace {
 
 int accumulate_locked(cyc_gramian_plan plan, const double* X, int64_t nrows, const double* mean,
                       double* U, double* sums, hipStream_t st);
 int col_sums_locked(cyc_gramian_plan plan, const double* X, int64_t nrows, double* sums,
                     double* sumsq, hipStream_t st);
+int wls_locked(cyc_wls_plan plan, const double* X, int64_t nrows, const double* y,
+               const double* w, double* U, hipStream_t st);
+int wls_check_weights(cyc_wls_plan plan, hipStream_t st);
 
-// CSR rows in chunks of about 1 GiB of dense rows: densify, then `dense`.
+// CSR rows of width p in chunks of about 1 GiB of dense rows: densify into
+// `chunk`, then `dense`.
 template <class F>
-int over_csr_chunks(cyc_gramian_plan plan, const int64_t* rowptr, const int32_t* colidx,
-                    const double* vals, int64_t nrows, hipStream_t st, F dense) {
-  const int p = plan->p;
+int over_csr_chunks(cyc::DeviceBuffer& chunk, int p, const int64_t* rowptr,
+                    const int32_t* colidx, const double* vals, int64_t nrows, hipStream_t st,
+                    F dense) {
   const int64_t R = std::max<int64_t>(256, ((int64_t)1 << 30) / (8 * (int64_t)p)) / 256 * 256;
   const int64_t rows = std::min<int64_t>(R, nrows);
-  if (int rc = plan->chunk.reserve(sizeof(double) * (size_t)rows * p)) return rc;
-  double* buf = (double*)plan->chunk.ptr;
+  if (int rc = chunk.reserve(sizeof(double) * (size_t)rows * p)) return rc;
+  double* buf = (double*)chunk.ptr;
   for (int64_t r0 = 0; r0 < nrows; r0 += R) {
     const int64_t nr = std::min<int64_t>(R, nrows - r0);
     CYC_HIP(hipMemsetAsync(buf, 0, sizeof(double) * (size_t)nr * p, st));
@@ -575,6 +714,12 @@ int over_csr_chunks(cyc_gramian_plan plan, const int64_t* rowptr, const int32_t*
     if (int rc = dense((const double*)buf, nr)) return rc;
   }
   return CYC_OK;
+}
+
+template <class F>
+int over_csr_chunks(cyc_gramian_plan plan, const int64_t* rowptr, const int32_t* colidx,
+                    const double* vals, int64_t nrows, hipStream_t st, F dense) {
+  return over_csr_chunks(plan->chunk, plan->p, rowptr, colidx, vals, nrows, st, dense);
 }
 
 }  // namespace
@@ -668,6 +813,74 @@ int cyc_col_moments_csr_dev(cyc_gramian_plan plan, const int64_t* rowptr, const 
 int cyc_col_sums_csr_dev(cyc_gramian_plan plan, const int64_t* rowptr, const int32_t* colidx,
                          const double* vals, int64_t nrows, double* sums, void* stream) {
   return cyc_col_moments_csr_dev(plan, rowptr, colidx, vals, nrows, sums, nullptr, stream);
+}
+
+int cyc_wls_plan_create(int32_t numFeatures, cyc_wls_plan* plan) {
+  CYC_REQUIRE(plan != nullptr, "plan must not be null");
+  // WeightedLeastSquares.MAX_NUM_FEATURES
+  CYC_REQUIRE(numFeatures <= 4096,
+              "In order to take the normal equation approach efficiently, we set the max "
+              "number of features to 4096 but got " + std::to_string(numFeatures) + ".");
+  CYC_REQUIRE(numFeatures > 0, "numFeatures must be positive");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    cyc::set_error("no HIP device visible");
+    return CYC_ERR_NO_DEVICE;
+  }
+  auto* p = new cyc_wls_plan_s();
+  p->p = numFeatures;
+  *plan = p;
+  return CYC_OK;
+}
+
+int cyc_wls_plan_destroy(cyc_wls_plan plan) {
+  delete plan;
+  return CYC_OK;
+}
+
+int cyc_wls_last_splits(cyc_wls_plan plan, int64_t* splits) {
+  CYC_REQUIRE(plan != nullptr && splits != nullptr, "plan and splits must not be null");
+  std::lock_guard<std::mutex> g(plan->mu);
+  *splits = plan->lastSplits;
+  return CYC_OK;
+}
+
+int cyc_wls_accumulate_dev(cyc_wls_plan plan, const double* X, int64_t nrows, const double* y,
+                           const double* w, double* U, void* stream) {
+  CYC_REQUIRE(plan != nullptr && U != nullptr, "plan and U must not be null");
+  CYC_REQUIRE(nrows >= 0, "nrows >= 0");
+  if (nrows == 0) return CYC_OK;
+  CYC_REQUIRE(X != nullptr && y != nullptr, "non-null rows and labels");
+  hipStream_t st = cyc::as_stream(stream);
+  std::lock_guard<std::mutex> g(plan->mu);
+  if (int rc = plan->flag.reserve(sizeof(int))) return rc;
+  CYC_HIP(hipMemsetAsync(plan->flag.ptr, 0, sizeof(int), st));
+  if (int rc = wls_locked(plan, X, nrows, y, w, U, st)) return rc;
+  return wls_check_weights(plan, st);
+}
+
+int cyc_wls_accumulate_csr_dev(cyc_wls_plan plan, const int64_t* rowptr, const int32_t* colidx,
+                               const double* vals, int64_t nrows, const double* y,
+                               const double* w, double* U, void* stream) {
+  CYC_REQUIRE(plan != nullptr && U != nullptr, "plan and U must not be null");
+  CYC_REQUIRE(nrows >= 0, "nrows >= 0");
+  if (nrows == 0) return CYC_OK;
+  CYC_REQUIRE(rowptr && colidx && vals && y, "non-null CSR arrays and labels");
+  hipStream_t st = cyc::as_stream(stream);
+  if (int rc = cyc::check_csr_indices(rowptr, colidx, nrows, plan->p, st)) return rc;
+  std::lock_guard<std::mutex> g(plan->mu);
+  if (int rc = plan->flag.reserve(sizeof(int))) return rc;
+  CYC_HIP(hipMemsetAsync(plan->flag.ptr, 0, sizeof(int), st));
+  int64_t done = 0;   // the chunks come in row order
+  int rc = over_csr_chunks(plan->chunk, plan->p, rowptr, colidx, vals, nrows, st,
+                           [&](const double* D, int64_t nr) {
+                             const int r = wls_locked(plan, D, nr, y + done, w ? w + done : nullptr,
+                                                      U, st);
+                             done += nr;
+                             return r;
+                           });
+  if (rc) return rc;
+  return wls_check_weights(plan, st);
 }
 
 int cyc_rowmatrix_dense_rows_dev(const double* X, const int64_t* rowptr, const double* vals,
@@ -798,6 +1011,43 @@ int accumulate_locked(cyc_gramian_plan plan, const double* X, int64_t nrows, con
   } else if (sums) {
     return col_sums_locked(plan, X, nrows, sums, nullptr, st);
   }
+  return CYC_OK;
+}
+
+// U += the weighted syrk of the augmented rows (width q = p + 2): the split
+// sizing of k_gram_tiles (two workgroups per CU), the same slabs and fold.
+int wls_locked(cyc_wls_plan plan, const double* X, int64_t nrows, const double* y,
+               const double* w, double* U, hipStream_t st) {
+  const int p = plan->p, q = p + 2;
+  const int tps = (q + TILE - 1) / TILE;
+  const int pairs = tps * (tps + 1) / 2;
+  const int64_t slots = 2 * (int64_t)cyc::device_cus();
+  const int64_t lo = std::max<int64_t>(1, (4 * slots + pairs - 1) / pairs);
+  int64_t splits = cyc::balanced_splits(pairs, lo, 2 * lo, slots);
+  splits = std::min<int64_t>(splits, std::max<int64_t>(1, nrows / 64));
+  const int64_t rps = cyc::round_up((nrows + splits - 1) / splits, KC);
+  splits = (nrows + rps - 1) / rps;
+  plan->lastSplits = splits;
+  if (int rc = plan->slab.reserve(sizeof(double) * (size_t)splits * pairs * TILE * TILE)) return rc;
+  {
+    cyc::KernelTimer timer("k_wls_tiles", st);
+    hipLaunchKernelGGL(k_wls_tiles, dim3(pairs, (unsigned)splits), dim3(GT), 0, st, X, nrows, p, y,
+                       w, tps, rps, (double*)plan->slab.ptr, (int*)plan->flag.ptr);
+    CYC_LAUNCH_CHECK("k_wls_tiles");
+  }
+  hipLaunchKernelGGL(k_gram_fold, dim3(TILE * TILE / 256, pairs), dim3(256), 0, st,
+                     (const double*)plan->slab.ptr, (int)splits, tps, q, U);
+  CYC_LAUNCH_CHECK("k_gram_fold");
+  return CYC_OK;
+}
+
+// Aggregator.add's require on the instance weight, once the call's kernels
+// have run: the flag read back on the call's stream.
+int wls_check_weights(cyc_wls_plan plan, hipStream_t st) {
+  int bad = 0;
+  CYC_HIP(hipMemcpyAsync(&bad, plan->flag.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+  CYC_HIP(hipStreamSynchronize(st));
+  CYC_REQUIRE(bad == 0, "Negative weight: instance weights have to be >= 0.0");
   return CYC_OK;
 }
 

@@ -348,6 +348,37 @@ int cyc_rowmatrix_dense_rows_dev(const double* X, const int64_t* rowptr, const d
 int cyc_sparse_covariance_finalize_dev(int32_t n, const double* U, int64_t m, const double* mean,
                                        double* G, void* stream);
 
+/* ------------------------------------------ WeightedLeastSquares moments */
+/* Replaces WeightedLeastSquares.Aggregator.add (ml/optim/
+ * WeightedLeastSquares.scala: spr(w, a, aaSum), axpy(w b, a, abSum),
+ * axpy(w, a, aSum), bSum, bbSum, wSum), the seqOp of the normal-equation
+ * LinearRegression fit.  For the augmented row z = [a, b, 1.0] of width
+ * q = numFeatures + 2 the call adds sum_r w_r z_r z_r^T to U, the packed
+ * upper triangle (column-major, U[j(j+1)/2 + i], i <= j) of q(q+1)/2
+ * doubles: aaSum is its leading block, abSum column numFeatures, bbSum entry
+ * (numFeatures, numFeatures), aSum column numFeatures + 1, bSum entry
+ * (numFeatures, numFeatures + 1) and wSum the last entry.  Moments of
+ * several calls (or ranks) merge by addition.  w may be NULL (all weights
+ * 1).  Rows of weight 0 contribute nothing, whatever their features hold.
+ * A negative or NaN weight fails the call with "requirement failed: Negative
+ * weight ..." (the call synchronizes the stream to read the flag).
+ * numFeatures > 4096 (WeightedLeastSquares.MAX_NUM_FEATURES) fails at plan
+ * creation with the reference's message.  fp64 MFMA syrk, deterministic
+ * fixed-order split-K reduction. */
+typedef struct cyc_wls_plan_s* cyc_wls_plan;
+
+int cyc_wls_plan_create(int32_t numFeatures, cyc_wls_plan* plan);
+int cyc_wls_plan_destroy(cyc_wls_plan plan);
+int cyc_wls_accumulate_dev(cyc_wls_plan plan, const double* X, int64_t nrows, const double* y,
+                           const double* w, double* U, void* stream);
+/* The same over CSR rows (densified in ~1 GiB chunks, as
+ * cyc_gramian_accumulate_csr_dev). */
+int cyc_wls_accumulate_csr_dev(cyc_wls_plan plan, const int64_t* rowptr, const int32_t* colidx,
+                               const double* vals, int64_t nrows, const double* y,
+                               const double* w, double* U, void* stream);
+/* Row splits (split-K slabs) of the plan's last syrk launch. */
+int cyc_wls_last_splits(cyc_wls_plan plan, int64_t* splits);
+
 /* ---------------------------------------------- logistic block aggregators */
 /* BinaryLogisticBlockAggregator.add (ml/optim/aggregator/
  * BinaryLogisticBlockAggregator.scala:81-145) and
