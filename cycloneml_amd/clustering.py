@@ -2,7 +2,9 @@
 
 Mirrors mllib/clustering/KMeans.scala (the Lloyd loop :240-349 and its
 parameters) and KMeansModel; the per-partition body runs in libcyclone
-(cycloneml_amd/csrc/kmeans.hip).  Data stays resident in HBM: `run` takes a
+(cycloneml_amd/csrc/kmeans.hip: the plan and the C ABI; kmeans_i8.hip,
+kmeans_fp64.hip, kmeans_sums.hip, kmeans_sparse.hip, kmeans_cos.hip: the
+tiers' kernels).  Data stays resident in HBM: `run` takes a
 torch CUDA fp64 tensor of shape (n, d) -- one process per GPU holding its
 shard of the rows (the Spark partitions assigned to that GPU).  When
 torch.distributed is initialised, the reduceByKey/collectAsMap merge

@@ -195,7 +195,7 @@ __global__ void k_cos_list_all(int32_t* __restrict__ list, unsigned int* __restr
 
 // CosineDistanceMeasure.findClosest (:421-447; stats == nullptr: the base
 // findClosest without statistics, :131-150) for the listed rows, one wave
-// per row.  As in the Euclidean exact tier (kmeans.hip k_assign_exact): the
+// per row.  As in the Euclidean exact tier (kmeans_fp64.hip k_assign_exact): the
 // loop state (best, bestIndex) changes only at an event, so 64 consecutive
 // centers are measured at once against the current state, a ballot finds
 // the first lane whose visit is an event (a return or an update), the state

@@ -718,6 +718,45 @@ def test_three_limb_candidate_tier(cuda, monkeypatch, n, d, k, cands3):
     np.testing.assert_array_equal(c.cpu().numpy(), rc)
 
 
+def test_per_call_switch_on_live_plan(cuda, monkeypatch):
+    """The per-call switches take effect per call on a live plan: one plan and
+    one row image (k > 96 and d <= 256, so the three-limb candidate tier
+    exists; near-duplicate centers, so candidates do), assign with
+    CYC_KMEANS_CANDS3=0 and again with it removed.  Index and cost bit-equal
+    between the calls and to the restatement; the tier's counter reports it
+    off (-1) for the first call and on (>= 0) for the second."""
+    import torch
+    from cycloneml_amd.clustering import row_norms
+    n, d, k = 4096, 64, 128
+    rng = np.random.default_rng(n + d + k + 7)
+    true_c = rng.normal(scale=1.5, size=(k, d))
+    X = true_c[rng.integers(0, k, n)] + rng.normal(size=(n, d))
+    C = X[:k].copy()
+    C[k // 2:k // 2 + 10] = C[:10] + 1e-9
+    Xd, Cd = _dev(X, cuda), _dev(C, cuda)
+    xn, cn = row_norms(Xd), row_norms(Cd)
+    p = _plan(d, k, n)
+    p.stats(Cd)
+    rows = p.rows(Xd)
+    got = []
+    for off in (True, False):
+        if off:
+            monkeypatch.setenv("CYC_KMEANS_CANDS3", "0")
+        else:
+            monkeypatch.delenv("CYC_KMEANS_CANDS3")
+        a = torch.empty(n, dtype=torch.int32, device=cuda)
+        c = torch.empty(n, dtype=torch.float64, device=cuda)
+        p.assign(Xd, xn, Cd, cn, a, c, count_exact=True, rows=rows)
+        torch.cuda.synchronize()
+        got.append((a.cpu().numpy(), c.cpu().numpy(), p.last_candidates3()))
+    ra, rc = _oracle_assign(X, C)
+    for a, c, _ in got:
+        np.testing.assert_array_equal(a, ra)
+        np.testing.assert_array_equal(c, rc)
+    assert got[0][2] == -1
+    assert got[1][2] >= 0
+
+
 @pytest.mark.timeout(900)
 def test_full_config_third_iteration(cuda):
     """BASELINE config 2 on bench.py's rows as the bench times it: two Lloyd
