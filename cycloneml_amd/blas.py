@@ -18,6 +18,9 @@ Every call copies its host operands to the device, runs a gfx950 kernel and
 copies the result back (netlib's synchronous host-pointer contract); it is
 the drop-in layer, not the hot path.  Invalid arguments raise
 IllegalArgumentException with XERBLA's message; there is no CPU fallback.
+A failed launch or copy raises CycloneError.  dnrm2 rescales when the plain
+sum of squares would overflow or underflow (netlib's value); dgemv / dspmv
+with alpha == 0 return beta * y without reading A or x.
 """
 import ctypes
 import os

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cctype>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -42,65 +43,76 @@ __global__ __launch_bounds__(256) void k_dgemm(int ta, int tb, int m, int n, int
   __shared__ double As[GT * AS];   // op(A)[i][p]
   __shared__ double Bs[GK * BS];   // op(B)[p][j]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i0 = blockIdx.x * GT, j0 = blockIdx.y * GT;
+  const int i0 = blockIdx.x * GT;
   const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
-  cyc_double4 acc[2][2];
+  // tile columns step by gridDim.y (one trip unless n > 64 * kMaxGridY)
+  for (int64_t jt = blockIdx.y; jt * GT < n; jt += gridDim.y) {
+    const int j0 = (int)(jt * GT);
+    cyc_double4 acc[2][2];
 #pragma unroll
-  for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = cyc_double4{0.0, 0.0, 0.0, 0.0};
-  for (int p0 = 0; p0 < k; p0 += GK) {
-    __syncthreads();
-    for (int e = tid; e < GT * GK; e += 256) {
-      // op(A)[i][p]: A is m x k ('N') or k x m ('T')
-      const int i = e / GK, p = e % GK;
-      const int gi = i0 + i, gp = p0 + p;
-      double v = 0.0;
-      if (gi < m && gp < k) v = ta ? A[gi * (size_t)lda + gp] : A[gp * (size_t)lda + gi];
-      As[i * AS + p] = v;
-    }
-    for (int e = tid; e < GT * GK; e += 256) {
-      const int p = e / GT, j = e % GT;
-      const int gj = j0 + j, gp = p0 + p;
-      double v = 0.0;
-      if (gj < n && gp < k) v = tb ? B[gp * (size_t)ldb + gj] : B[gj * (size_t)ldb + gp];
-      Bs[p * BS + j] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < GK; kk += 4) {
-      double a[2], b[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        a[q] = As[(wi + q * 16 + (lane & 15)) * AS + kk + (lane >> 4)];
-        b[q] = Bs[(kk + (lane >> 4)) * BS + wj + q * 16 + (lane & 15)];
+      for (int b = 0; b < 2; ++b) acc[a][b] = cyc_double4{0.0, 0.0, 0.0, 0.0};
+    for (int p0 = 0; p0 < k; p0 += GK) {
+      __syncthreads();
+      for (int e = tid; e < GT * GK; e += 256) {
+        // op(A)[i][p]: A is m x k ('N') or k x m ('T')
+        const int i = e / GK, p = e % GK;
+        const int gi = i0 + i, gp = p0 + p;
+        double v = 0.0;
+        if (gi < m && gp < k) v = ta ? A[gi * (size_t)lda + gp] : A[gp * (size_t)lda + gi];
+        As[i * AS + p] = v;
       }
+      for (int e = tid; e < GT * GK; e += 256) {
+        const int p = e / GT, j = e % GT;
+        const int gj = j0 + j, gp = p0 + p;
+        double v = 0.0;
+        if (gj < n && gp < k) v = tb ? B[gp * (size_t)ldb + gj] : B[gj * (size_t)ldb + gp];
+        Bs[p * BS + j] = v;
+      }
+      __syncthreads();
 #pragma unroll
-      for (int qa = 0; qa < 2; ++qa)
+      for (int kk = 0; kk < GK; kk += 4) {
+        double a[2], b[2];
 #pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-          acc[qa][qb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[qa], b[qb], acc[qa][qb], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int qa = 0; qa < 2; ++qa)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int gi = i0 + wi + qa * 16 + (lane >> 4) + 4 * r;
-        const int gj = j0 + wj + qb * 16 + (lane & 15);
-        if (gi < m && gj < n) {
-          double* c = C + gj * (size_t)ldc + gi;
-          // netlib: beta == 0 overwrites C (no 0*NaN), else alpha*temp + beta*c
-          *c = (beta == 0.0) ? alpha * acc[qa][qb][r] : alpha * acc[qa][qb][r] + beta * *c;
+        for (int q = 0; q < 2; ++q) {
+          a[q] = As[(wi + q * 16 + (lane & 15)) * AS + kk + (lane >> 4)];
+          b[q] = Bs[(kk + (lane >> 4)) * BS + wj + q * 16 + (lane & 15)];
         }
+#pragma unroll
+        for (int qa = 0; qa < 2; ++qa)
+#pragma unroll
+          for (int qb = 0; qb < 2; ++qb)
+            acc[qa][qb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[qa], b[qb], acc[qa][qb], 0, 0, 0);
       }
+    }
+#pragma unroll
+    for (int qa = 0; qa < 2; ++qa)
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int gi = i0 + wi + qa * 16 + (lane >> 4) + 4 * r;
+          const int gj = j0 + wj + qb * 16 + (lane & 15);
+          if (gi < m && gj < n) {
+            double* c = C + gj * (size_t)ldc + gi;
+            // netlib: beta == 0 overwrites C (no 0*NaN), else alpha*temp + beta*c
+            *c = (beta == 0.0) ? alpha * acc[qa][qb][r] : alpha * acc[qa][qb][r] + beta * *c;
+          }
+        }
+  }
 }
 
+// Columns ride on gridDim.y, where HIP promises room for kMaxGridY blocks
+// and no more: the kernels here and k_dgemm step over the columns by
+// gridDim.y, so any n is one launch whatever the runtime's own limit.
+constexpr int kMaxGridY = 65535;
+
 __global__ void k_scale_matrix(int m, int n, double beta, double* C, int ldc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-  if (i < m) C[j * (size_t)ldc + i] = beta == 0.0 ? 0.0 : beta * C[j * (size_t)ldc + i];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  for (int64_t j = blockIdx.y; j < n; j += gridDim.y)
+    C[j * (size_t)ldc + i] = beta == 0.0 ? 0.0 : beta * C[j * (size_t)ldc + i];
 }
 
 // y(i) = beta y(i) + alpha sum_j A(i,j) x(j), one thread per row ('N').
@@ -134,28 +146,37 @@ __global__ void k_dgemv_t(int m, int n, double alpha, const double* __restrict__
 // netlib dspr / dsyr (upper or lower): a(i,j) += x(i) * (alpha x(j))
 __global__ void k_dspr(int upper, int n, double alpha, const double* __restrict__ x,
                        double* __restrict__ ap) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-  if (i >= n || x[j] == 0.0) return;
-  const double t = alpha * x[j];
-  if (upper) {
-    if (i <= j) ap[(size_t)j * (j + 1) / 2 + i] += x[i] * t;
-  } else {
-    if (i >= j) ap[(size_t)j * (2 * (size_t)n - j + 1) / 2 + (i - j)] += x[i] * t;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (int64_t j = blockIdx.y; j < n; j += gridDim.y) {
+    if (x[j] == 0.0) continue;
+    const double t = alpha * x[j];
+    if (upper) {
+      if (i <= j) ap[(size_t)j * (j + 1) / 2 + i] += x[i] * t;
+    } else {
+      if (i >= j) ap[(size_t)j * (2 * (size_t)n - j + 1) / 2 + (i - j)] += x[i] * t;
+    }
   }
 }
 
 __global__ void k_dsyr(int upper, int n, double alpha, const double* __restrict__ x,
                        double* __restrict__ a, int lda) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-  if (i >= n || x[j] == 0.0) return;
-  if (upper ? i <= j : i >= j) a[j * (size_t)lda + i] += x[i] * (alpha * x[j]);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (int64_t j = blockIdx.y; j < n; j += gridDim.y) {
+    if (x[j] == 0.0) continue;
+    if (upper ? i <= j : i >= j) a[j * (size_t)lda + i] += x[i] * (alpha * x[j]);
+  }
 }
 
 __global__ void k_dger(int m, int n, double alpha, const double* __restrict__ x,
                        const double* __restrict__ y, double* __restrict__ a, int lda) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-  if (i >= m || y[j] == 0.0) return;
-  a[j * (size_t)lda + i] += x[i] * (alpha * y[j]);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  for (int64_t j = blockIdx.y; j < n; j += gridDim.y) {
+    if (y[j] == 0.0) continue;
+    a[j * (size_t)lda + i] += x[i] * (alpha * y[j]);
+  }
 }
 
 // y = alpha AP x + beta y, AP symmetric packed (netlib dspmv), thread per row.
@@ -201,6 +222,43 @@ __global__ void k_dot_final(int nb, double* __restrict__ out) {
   out[0] = s;
 }
 
+// dnrm2's scaled pass, taken only when the plain sum of squares overflowed
+// or may have lost squares to underflow.  The same grid and trees as k_dot:
+// pass 0 leaves max |x(i)| in out[1 + b] (k_max_final folds the blocks),
+// pass 1 the sum of (x(i) 2^-e)^2, e the exponent of that maximum, so every
+// scaled element is below 2 and the largest is at least 1.  A power of two
+// scales exactly; the squares that still underflow are below 2^-1022 beside
+// a sum of at least 1.
+__global__ __launch_bounds__(256) void k_nrm2_scaled(int n, const double* __restrict__ x,
+                                                     double* __restrict__ out, int pass, int e) {
+  __shared__ double sh[256];
+  double a = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    if (pass == 0) {
+      a = fmax(a, fabs(x[i]));
+    } else {
+      const double v = ldexp(x[i], -e);
+      a += v * v;
+    }
+  }
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s)
+      sh[threadIdx.x] = pass == 0 ? fmax(sh[threadIdx.x], sh[threadIdx.x + s])
+                                  : sh[threadIdx.x] + sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[1 + blockIdx.x] = sh[0];
+}
+
+__global__ void k_max_final(int nb, double* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int b = 0; b < nb; ++b) s = fmax(s, out[1 + b]);
+  out[0] = s;
+}
+
 __global__ void k_axpy(int n, double a, const double* __restrict__ x, double* __restrict__ y) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] = y[i] + a * x[i];
@@ -233,6 +291,7 @@ Ctx* ctx() {
     }
     c = n;
   }
+  (void)hipGetLastError();  // an earlier call's error is not this call's launch status
   return c;
 }
 
@@ -289,6 +348,14 @@ bool fail(const char* what) {
                  hipGetErrorString(hipGetLastError()));
   return false;
 }
+// the status of the launch just made (hipLaunchKernelGGL returns none)
+bool launched(const char* kernel) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return true;
+  cyc::set_error(std::string("cyclone BLAS: launch of ") + kernel + " failed: " +
+                 hipGetErrorString(e));
+  return false;
+}
 
 bool gemm(char ta, char tb, int m, int n, int k, double alpha, const double* A, int lda,
           const double* B, int ldb, double beta, double* C, int ldc) {
@@ -311,19 +378,41 @@ bool gemm(char ta, char tb, int m, int n, int k, double alpha, const double* A, 
   double* dC = c->reserve(2, (size_t)m * n);
   if (!dC || !h2d(dC, C, m, n, ldc, c->st)) return fail("copy C");
   if (alpha == 0.0 || k == 0) {
-    hipLaunchKernelGGL(k_scale_matrix, dim3((m + 255) / 256, n), dim3(256), 0, c->st, m, n, beta,
-                       dC, m);
+    hipLaunchKernelGGL(k_scale_matrix, dim3((m + 255) / 256, std::min(n, kMaxGridY)), dim3(256),
+                       0, c->st, m, n, beta, dC, m);
+    if (!launched("k_scale_matrix")) return false;
   } else {
     const int ar = nota ? m : k, ac = nota ? k : m, br = notb ? k : n, bc = notb ? n : k;
     double* dA = c->reserve(0, (size_t)ar * ac);
     double* dB = c->reserve(1, (size_t)br * bc);
     if (!dA || !dB || !h2d(dA, A, ar, ac, lda, c->st) || !h2d(dB, B, br, bc, ldb, c->st))
       return fail("copy A/B");
-    hipLaunchKernelGGL(k_dgemm, dim3((m + GT - 1) / GT, (n + GT - 1) / GT), dim3(256), 0, c->st,
-                       nota ? 0 : 1, notb ? 0 : 1, m, n, k, alpha, dA, ar, dB, br, beta, dC, m);
+    hipLaunchKernelGGL(k_dgemm, dim3((m + GT - 1) / GT, std::min((n + GT - 1) / GT, kMaxGridY)),
+                       dim3(256), 0, c->st, nota ? 0 : 1, notb ? 0 : 1, m, n, k, alpha, dA, ar, dB,
+                       br, beta, dC, m);
+    if (!launched("k_dgemm")) return false;
   }
   if (!d2h(C, dC, m, n, ldc, c->st) || hipStreamSynchronize(c->st) != hipSuccess)
     return fail("dgemm");
+  return true;
+}
+
+// y := beta y on the device (dgemv / dspmv with alpha == 0): only y is
+// staged; beta == 0 stores zeros without reading y's values.
+bool scale_y(int n, double beta, double* y, int incy) {
+  Ctx* c = ctx();
+  if (!c) return fail("stream");
+  std::vector<double> hy = gather(n, y, incy);
+  double* dy = c->reserve(2, n);
+  if (!dy || hipMemcpyAsync(dy, hy.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->st))
+    return fail("copy");
+  hipLaunchKernelGGL(k_scale_matrix, dim3((n + 255) / 256, 1), dim3(256), 0, c->st, n, 1, beta, dy,
+                     n);
+  if (!launched("k_scale_matrix")) return false;
+  if (hipMemcpyAsync(hy.data(), dy, sizeof(double) * n, hipMemcpyDeviceToHost, c->st) ||
+      hipStreamSynchronize(c->st))
+    return fail("scale y");
+  scatter(n, hy, y, incy);
   return true;
 }
 
@@ -340,6 +429,7 @@ bool gemv(char t, int m, int n, double alpha, const double* A, int lda, const do
   if (info) return xerbla("DGEMV ", info);
   if (m == 0 || n == 0 || (alpha == 0.0 && beta == 1.0)) return true;
   const int lenx = t == 'N' ? n : m, leny = t == 'N' ? m : n;
+  if (alpha == 0.0) return scale_y(leny, beta, y, incy);  // netlib: A and x not referenced
   Ctx* c = ctx();
   if (!c) return fail("stream");
   std::vector<double> hx = gather(lenx, x, incx), hy = gather(leny, y, incy);
@@ -357,6 +447,7 @@ bool gemv(char t, int m, int n, double alpha, const double* A, int lda, const do
   else
     hipLaunchKernelGGL(k_dgemv_t, dim3((n + 3) / 4), dim3(256), 0, c->st, m, n, a, dA, m, dx, beta,
                        dy);
+  if (!launched(t == 'N' ? "k_dgemv_n" : "k_dgemv_t")) return false;
   if (hipMemcpyAsync(hy.data(), dy, sizeof(double) * leny, hipMemcpyDeviceToHost, c->st) ||
       hipStreamSynchronize(c->st))
     return fail("dgemv");
@@ -398,10 +489,11 @@ bool rank1(const char* name, int kind, char uplo, int m, int n, double alpha, co
     ok = ok && hipMemcpyAsync(dy, hy.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->st) ==
                    hipSuccess;
   if (!ok) return fail("copy");
-  dim3 g((rows + 255) / 256, n);
+  dim3 g((rows + 255) / 256, std::min(n, kMaxGridY));
   if (kind == 0) hipLaunchKernelGGL(k_dspr, g, dim3(256), 0, c->st, upper, n, alpha, dx, dA);
   else if (kind == 1) hipLaunchKernelGGL(k_dsyr, g, dim3(256), 0, c->st, upper, n, alpha, dx, dA, n);
   else hipLaunchKernelGGL(k_dger, g, dim3(256), 0, c->st, m, n, alpha, dx, dy, dA, m);
+  if (!launched(kind == 0 ? "k_dspr" : kind == 1 ? "k_dsyr" : "k_dger")) return false;
   ok = (kind == 0 ? hipMemcpyAsync(a, dA, sizeof(double) * asz, hipMemcpyDeviceToHost, c->st) ==
                         hipSuccess
                   : d2h(a, dA, rows, n, lda, c->st)) &&
@@ -440,16 +532,52 @@ bool level1(int op, int n, double a, const double* x, int incx, double* y, int i
   if (op == 0 || op == 4) {
     const int nb = (int)std::min<int64_t>(kDotBlocks, ((int64_t)n + 2047) / 2048);
     hipLaunchKernelGGL(k_dot, dim3(nb), dim3(256), 0, c->st, n, dx, dy, dr, op == 4);
+    if (!launched("k_dot")) return false;
     hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(64), 0, c->st, nb, dr);
+    if (!launched("k_dot_final")) return false;
     double r = 0.0;
     if (hipMemcpyAsync(&r, dr, sizeof(double), hipMemcpyDeviceToHost, c->st) ||
         hipStreamSynchronize(c->st))
       return fail("dot");
-    *result = op == 4 ? std::sqrt(r) : r;
+    if (op == 0) {
+      *result = r;
+      return true;
+    }
+    // dnrm2.  The plain sum stands whenever it is finite and at least
+    // kNrm2Safe: a square lost to underflow is below 2^-1022, so fewer than
+    // 2^31 of them add less than 2^-991, under 2^-91 of such a sum.  NaN in
+    // gives a NaN sum (squares are never negative, so no inf - inf).
+    constexpr double kNrm2Safe = 0x1p-900;
+    if (r != r || (r >= kNrm2Safe && r <= DBL_MAX)) {
+      *result = std::sqrt(r);
+      return true;
+    }
+    double amax = 0.0;
+    hipLaunchKernelGGL(k_nrm2_scaled, dim3(nb), dim3(256), 0, c->st, n, dx, dr, 0, 0);
+    if (!launched("k_nrm2_scaled")) return false;
+    hipLaunchKernelGGL(k_max_final, dim3(1), dim3(64), 0, c->st, nb, dr);
+    if (!launched("k_max_final")) return false;
+    if (hipMemcpyAsync(&amax, dr, sizeof(double), hipMemcpyDeviceToHost, c->st) ||
+        hipStreamSynchronize(c->st))
+      return fail("dnrm2");
+    if (amax == 0.0 || std::isinf(amax)) {  // all zeros, or an Inf and no NaN
+      *result = amax;
+      return true;
+    }
+    const int e = std::ilogb(amax);
+    hipLaunchKernelGGL(k_nrm2_scaled, dim3(nb), dim3(256), 0, c->st, n, dx, dr, 1, e);
+    if (!launched("k_nrm2_scaled")) return false;
+    hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(64), 0, c->st, nb, dr);
+    if (!launched("k_dot_final")) return false;
+    if (hipMemcpyAsync(&r, dr, sizeof(double), hipMemcpyDeviceToHost, c->st) ||
+        hipStreamSynchronize(c->st))
+      return fail("dnrm2");
+    *result = std::ldexp(std::sqrt(r), e);
     return true;
   }
   if (op == 1) hipLaunchKernelGGL(k_axpy, g, dim3(256), 0, c->st, n, a, dx, dy);
   else hipLaunchKernelGGL(k_scal, g, dim3(256), 0, c->st, n, a, dx);
+  if (!launched(op == 1 ? "k_axpy" : "k_scal")) return false;
   double* src = op == 1 ? dy : dx;
   std::vector<double> to;
   double* dst = op == 1 ? out_view(n, y, incy, to) : out_view(n, const_cast<double*>(x), incx, to);
@@ -471,6 +599,7 @@ bool spmv(char uplo, int n, double alpha, const double* ap, const double* x, int
   else if (incy == 0) info = 9;
   if (info) return xerbla("DSPMV ", info);
   if (n == 0 || (alpha == 0.0 && beta == 1.0)) return true;
+  if (alpha == 0.0) return scale_y(n, beta, y, incy);  // netlib: AP and x not referenced
   Ctx* c = ctx();
   if (!c) return fail("stream");
   std::vector<double> hx = gather(n, x, incx), hy = gather(n, y, incy);
@@ -485,6 +614,7 @@ bool spmv(char uplo, int n, double alpha, const double* ap, const double* x, int
     return fail("copy");
   hipLaunchKernelGGL(k_dspmv, dim3((n + 255) / 256), dim3(256), 0, c->st, uplo == 'U', n, alpha, dA,
                      dx, beta, dy);
+  if (!launched("k_dspmv")) return false;
   if (hipMemcpyAsync(hy.data(), dy, sizeof(double) * n, hipMemcpyDeviceToHost, c->st) ||
       hipStreamSynchronize(c->st))
     return fail("dspmv");

@@ -28,6 +28,11 @@
  * XERBLA's parameter numbering: the call returns without touching its
  * outputs and the message (" ** On entry to DGEMM  parameter number 8 had an
  * illegal value") is available from libcyclone's cyc_last_error().
+ * A kernel launch or copy that fails is reported there as well; any number
+ * of columns is one launch (columns are not bound by the grid's y limit).
+ * dnrm2_ returns netlib's value where the plain sum of squares would
+ * overflow or underflow (a scaled second pass); NaN in gives NaN, Inf +inf.
+ * dgemv_ / dspmv_ with alpha == 0 return beta * y without reading A or x.
  *
  * This layer pays a PCIe round trip per call; it exists so that every
  * netlib call site works unchanged.  The hot paths bind cyclone.h's
