@@ -109,6 +109,19 @@ SIGNATURES = {
     "cyc_wls_accumulate_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "cyc_wls_accumulate_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "cyc_wls_last_splits": (ctypes.c_int, [_vp, _pi64]),
+    "cyc_glm_plan_create": (ctypes.c_int, [_i32, _i32, _f64, _f64, _i32, ctypes.POINTER(_vp)]),
+    "cyc_glm_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_glm_reweight_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _vp,
+                                            _vp, _vp]),
+    "cyc_glm_reweight_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                                _f64, _i32, _vp, _vp, _vp]),
+    "cyc_glm_mean_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _f64, _i32, _vp, _vp]),
+    "cyc_glm_mean_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f64, _i32, _vp,
+                                            _vp]),
+    "cyc_glm_stats_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _f64,
+                                         _vp, _vp]),
+    "cyc_glm_stats_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64,
+                                             _i32, _f64, _vp, _vp]),
     "cyc_logistic_plan_create": (ctypes.c_int, [_i32, _i32, ctypes.c_int, ctypes.c_int,
                                                 ctypes.POINTER(_vp)]),
     "cyc_logistic_plan_destroy": (ctypes.c_int, [_vp]),

@@ -154,15 +154,19 @@ class WeightedLeastSquares:
         self.tol = float(tol)
 
     # -- the aggregate: one weighted syrk per shard, one all-reduce ---------------
-    def moments(self, X, y, w=None):
+    def moments(self, X, y, w=None, plan: Optional[WLSPlan] = None):
         """(U, count): the packed moments of this fit's rows, merged over
-        ranks, on the device; count is the number of rows over ranks."""
+        ranks, on the device; count is the number of rows over ranks.  plan:
+        a caller's WLSPlan of these rows' width, kept open (a fit repeated
+        over the same rows, as IRLS does, holds one)."""
         from .linalg import CSRRows
         torch = _torch()
         sparse = isinstance(X, CSRRows)
         k = X.numCols if sparse else int(X.shape[1])
         n = X.n if sparse else int(X.shape[0])
-        plan = WLSPlan(k)
+        own = plan is None
+        if own:
+            plan = WLSPlan(k)
         try:
             # the last slot carries the row count through the same all-reduce
             buf = torch.zeros(plan.packedSize + 1, dtype=torch.float64, device=X.device)
@@ -174,15 +178,16 @@ class WeightedLeastSquares:
             buf[plan.packedSize] = n
             parallel.allreduce_(buf)       # treeAggregate combOp: merge by addition
         finally:
-            plan.close()
+            if own:
+                plan.close()
         return U, int(buf[plan.packedSize].item())
 
-    def fit(self, X, y, w=None) -> WeightedLeastSquaresModel:
+    def fit(self, X, y, w=None, plan: Optional[WLSPlan] = None) -> WeightedLeastSquaresModel:
         """X: this rank's device rows (fp64 tensor n x k, or linalg.CSRRows);
         y, w: device fp64 vectors (w None: unit weights)."""
         from .linalg import CSRRows
         k = X.numCols if isinstance(X, CSRRows) else int(X.shape[1])
-        U, count = self.moments(X, y, w)
+        U, count = self.moments(X, y, w, plan)
         return self.solve(U.cpu().numpy(), k, count=count)
 
     # -- the driver side ----------------------------------------------------------

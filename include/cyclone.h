@@ -379,6 +379,82 @@ int cyc_wls_accumulate_csr_dev(cyc_wls_plan plan, const int64_t* rowptr, const i
 /* Row splits (split-K slabs) of the plan's last syrk launch. */
 int cyc_wls_last_splits(cyc_wls_plan plan, int64_t* splits);
 
+/* ------------------------------------- GeneralizedLinearRegression (IRLS) */
+/* The per-row passes of ml/regression/GeneralizedLinearRegression.scala
+ * around the WLS aggregate above: FamilyAndLink.initialize / reweightFunc
+ * (the instances of one IterativelyReweightedLeastSquares iteration), the
+ * fitted mean, and the training summary's reductions.  family and link are
+ * the codes below; CYC_GLM_TWEEDIE takes CYC_GLM_POWER with linkPower, and
+ * variancePower 0 / 1 / 2 is gaussian / poisson / gamma, linkPower 0 / 1 /
+ * -1 / 0.5 is log / identity / inverse / sqrt (Family.fromParams,
+ * Link.fromParams).  Plan creation fails on a pair the reference rejects, on
+ * variancePower in (0, 1) or negative, and on numFeatures outside 1..4096.
+ * Rows are dense row-major X (nrows x numFeatures) or CSR; y, w (NULL: 1)
+ * and offset (NULL: 0) are device vectors of nrows doubles, coef a device
+ * vector of numFeatures doubles.  eta = dot(x, coef) + intercept + offset;
+ * with coef == NULL no features are read (X or the CSR arrays may be NULL)
+ * and eta = intercept + offset. */
+enum {
+  CYC_GLM_GAUSSIAN = 0,
+  CYC_GLM_BINOMIAL = 1,
+  CYC_GLM_POISSON = 2,
+  CYC_GLM_GAMMA = 3,
+  CYC_GLM_TWEEDIE = 4
+};
+enum {
+  CYC_GLM_IDENTITY = 0,
+  CYC_GLM_LOG = 1,
+  CYC_GLM_INVERSE = 2,
+  CYC_GLM_LOGIT = 3,
+  CYC_GLM_PROBIT = 4,
+  CYC_GLM_CLOGLOG = 5,
+  CYC_GLM_SQRT = 6,
+  CYC_GLM_POWER = 7
+};
+typedef struct cyc_glm_plan_s* cyc_glm_plan;
+
+int cyc_glm_plan_create(int32_t family, int32_t link, double variancePower, double linkPower,
+                        int32_t numFeatures, cyc_glm_plan* plan);
+int cyc_glm_plan_destroy(cyc_glm_plan plan);
+/* One row -> (z, wOut), the label and weight of the next WLS fit.
+ * init != 0 (FamilyAndLink.initialize; coef and the features are not read):
+ *   mu = family.initialize(y, w), z = link(mu) - offset, wOut = w.
+ * init == 0 (reweightFunc): mu = project(unlink(eta)), g = link.deriv(mu),
+ *   z = eta - offset + (y - mu) g, wOut = w / (g g V(mu)); a row of weight 0
+ *   gives z = 0, wOut = 0 and its features are not read.
+ * A label outside the family's domain fails the call with "requirement
+ * failed: ..." (the call synchronizes the stream to read the flag). */
+int cyc_glm_reweight_dev(cyc_glm_plan plan, const double* X, int64_t nrows, const double* y,
+                         const double* w, const double* offset, const double* coef,
+                         double intercept, int32_t init, double* z, double* wOut, void* stream);
+int cyc_glm_reweight_csr_dev(cyc_glm_plan plan, const int64_t* rowptr, const int32_t* colidx,
+                             const double* vals, int64_t nrows, const double* y, const double* w,
+                             const double* offset, const double* coef, double intercept,
+                             int32_t init, double* z, double* wOut, void* stream);
+/* out[r] = project(unlink(eta_r)) (predict), or eta_r with linkPrediction. */
+int cyc_glm_mean_dev(cyc_glm_plan plan, const double* X, int64_t nrows, const double* offset,
+                     const double* coef, double intercept, int32_t linkPrediction, double* out,
+                     void* stream);
+int cyc_glm_mean_csr_dev(cyc_glm_plan plan, const int64_t* rowptr, const int32_t* colidx,
+                         const double* vals, int64_t nrows, const double* offset,
+                         const double* coef, double intercept, int32_t linkPrediction,
+                         double* out, void* stream);
+/* sums (6 device doubles, overwritten) = { sum w, sum w y, the deviance,
+ * Pearson's sum w (y - mu)^2 / V(mu), the log-likelihood behind family.aic
+ * (gamma: at `dispersion`; 0 for gaussian and tweedie), sum log w } with
+ * mu = project(unlink(eta)) (project != 0) or unlink(eta) (the null
+ * deviance).  A row of weight 0 adds only its log w and its features are
+ * not read.  Per-wave partials folded in a fixed order: two calls on the
+ * same input give the same bits. */
+int cyc_glm_stats_dev(cyc_glm_plan plan, const double* X, int64_t nrows, const double* y,
+                      const double* w, const double* offset, const double* coef,
+                      double intercept, int32_t project, double dispersion, double* sums,
+                      void* stream);
+int cyc_glm_stats_csr_dev(cyc_glm_plan plan, const int64_t* rowptr, const int32_t* colidx,
+                          const double* vals, int64_t nrows, const double* y, const double* w,
+                          const double* offset, const double* coef, double intercept,
+                          int32_t project, double dispersion, double* sums, void* stream);
+
 /* ---------------------------------------------- logistic block aggregators */
 /* BinaryLogisticBlockAggregator.add (ml/optim/aggregator/
  * BinaryLogisticBlockAggregator.scala:81-145) and
