@@ -19,3 +19,7 @@ from .regression import (  # noqa: F401
     WeightedLeastSquares,
     WeightedLeastSquaresModel,
 )
+from .regression_summary import (  # noqa: F401
+    LinearRegressionSummary,
+    LinearRegressionTrainingSummary,
+)

@@ -122,6 +122,13 @@ SIGNATURES = {
                                          _vp, _vp]),
     "cyc_glm_stats_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64,
                                              _i32, _f64, _vp, _vp]),
+    "cyc_linreg_predict_dev": (ctypes.c_int, [_vp, _i64, _i32, _vp, _f64, _vp, _vp]),
+    "cyc_linreg_predict_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _f64, _vp,
+                                                  _vp]),
+    "cyc_linreg_stats_dev": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _f64, _f64, _vp, _vp,
+                                            _vp]),
+    "cyc_linreg_stats_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _f64,
+                                                _f64, _vp, _vp, _vp]),
     "cyc_logistic_plan_create": (ctypes.c_int, [_i32, _i32, ctypes.c_int, ctypes.c_int,
                                                 ctypes.POINTER(_vp)]),
     "cyc_logistic_plan_destroy": (ctypes.c_int, [_vp]),

@@ -14,6 +14,14 @@ side on the packed moments, in numpy: standardization, the L2 diagonal, the
 Cholesky solve with its inverse's diagonal, and the quasi-Newton solver
 (cycloneml_amd.optimize's LBFGS / OWLQN) for L1 and for singular systems.
 
+Every other LinearRegression fit (solver "l-bfgs", "auto" above 4096
+features, loss "huber") is the reference's quasi-Newton branch:
+`LinearRegression.train_from_summary` drives LBFGS / OWLQN / LBFGSB over a
+cost callable, which on the device is `BlockCost`: one
+LeastSquaresBlockAggregator / HuberBlockAggregator add over the shard plus
+its all-reduce per evaluation.  Predictions over CSR rows and the model's
+summary come from libcyclone's evaluate pass (regression_summary.py).
+
 The reference's sources are not vendored; the semantics are restated and
 pinned by the WeightedLeastSquaresSuite known answers in tests/.
 """
@@ -336,23 +344,64 @@ class LinearRegressionModel:
     LinearRegression."""
 
     def __init__(self, coefficients, intercept: float, scale: float = 1.0,
-                 objectiveHistory=(0.0,), diagInvAtWA=(0.0,)):
+                 objectiveHistory=(0.0,), diagInvAtWA=(0.0,), fitIntercept: bool = True):
         self.coefficients = np.asarray(coefficients, dtype=np.float64)
         self.intercept = float(intercept)
         self.scale = float(scale)
         self.objectiveHistory = np.asarray(objectiveHistory, dtype=np.float64)
         self.diagInvAtWA = np.asarray(diagInvAtWA, dtype=np.float64)
+        self.fitIntercept = bool(fitIntercept)
         self._coef_dev = None
+        self._inference = False    # diagInvAtWA of an unregularized normal-equation fit
+        self._training = None      # (X, y, weights, yMean) of the fit, for `summary`
+        self._summary = None
 
     @property
     def numFeatures(self) -> int:
         return int(self.coefficients.shape[0])
 
+    def _coefficients_on(self, device):
+        torch = _torch()
+        if self._coef_dev is None or self._coef_dev.device != device:
+            self._coef_dev = torch.from_numpy(self.coefficients).to(device)
+        return self._coef_dev
+
+    @property
+    def hasSummary(self) -> bool:
+        return self._training is not None
+
+    @property
+    def summary(self):
+        """LinearRegressionTrainingSummary of the rows this model was fitted
+        on, built on first access: one stats pass, none inside fit."""
+        if self._training is None:
+            raise RuntimeError("No training summary available for this LinearRegressionModel")
+        if self._summary is None:
+            from .regression_summary import LinearRegressionTrainingSummary
+            X, y, w, yMean = self._training
+            self._summary = LinearRegressionTrainingSummary(self, X, y, w, yMean,
+                                                            self.objectiveHistory)
+        return self._summary
+
+    def evaluate(self, X, y, weights=None):
+        """LinearRegressionSummary of this model on (X, y, weights): X an fp64
+        device tensor n x numFeatures or linalg.CSRRows."""
+        from .regression_summary import LinearRegressionSummary
+        return LinearRegressionSummary(self, X, y, weights)
+
     def predict(self, X):
         """dot(features, coefficients) + intercept: for device rows (fp64
-        tensor n x numFeatures) a device vector of n predictions; for one
-        host vector a float."""
+        tensor n x numFeatures, or linalg.CSRRows) a device vector of n
+        predictions; for one host vector a float."""
+        from .linalg import CSRRows
         torch = _torch()
+        if isinstance(X, CSRRows):
+            from .regression_summary import linreg_predict
+            if X.numCols != self.numFeatures:
+                raise N.IllegalArgumentException(
+                    f"requirement failed: expected {self.numFeatures} features but got "
+                    f"{X.numCols}")
+            return linreg_predict(X, self._coefficients_on(X.device), self.intercept)
         if isinstance(X, torch.Tensor):
             if self._coef_dev is None or self._coef_dev.device != X.device:
                 self._coef_dev = torch.from_numpy(self.coefficients).to(X.device)
@@ -365,17 +414,75 @@ class LinearRegressionModel:
         return float(np.dot(v, self.coefficients) + self.intercept)
 
 
+class _L2:
+    """L2Regularization over the first nreg parameters: 0.5 regParam sum c_j^2;
+    with std given (standardization = false) c_j^2 / std_j^2, 0 where std_j
+    is 0 (classification._L2 restated for one coefficient set)."""
+
+    def __init__(self, regParam, nreg, std=None):
+        self.regParam, self.nreg = float(regParam), int(nreg)
+        self.mult = np.ones(nreg) if std is None else _safe_div(1.0, np.asarray(std) ** 2)
+
+    def calculate(self, x):
+        t = x[:self.nreg] * self.mult
+        g = np.zeros_like(x)
+        g[:self.nreg] = self.regParam * t
+        return 0.5 * self.regParam * float(np.dot(x[:self.nreg], t)), g
+
+
+class BlockCost:
+    """RDDLossFunction.calculate over one device shard for the parameters of
+    the STANDARDIZED problem, without the regularization term: the rows stay
+    as they are, the parameters go in multiplied by `scale` (inverseStd for
+    the linear terms, 1 for intercept and sigma slots) and the gradient comes
+    back multiplied by it.  One evaluation is one aggregator add over the
+    block plus the aggregator's all-reduce.  make_aggregator(raw parameters)
+    returns a fresh optim.DifferentiableLossAggregator (least squares and
+    Huber here; hinge and AFT take the same shape)."""
+
+    def __init__(self, block, make_aggregator, scale):
+        self.block = block
+        self.make_aggregator = make_aggregator
+        self.scale = np.asarray(scale, dtype=np.float64)
+        self.evaluations = 0
+
+    def __call__(self, x):
+        agg = self.make_aggregator(x * self.scale)
+        agg.add(self.block)
+        agg.allreduce()
+        self.evaluations += 1
+        return agg.loss, agg.gradient * self.scale
+
+
 class LinearRegression:
-    """LinearRegression estimator over device-resident rows.  solver "normal"
-    (and "auto" up to 4096 features) is the WeightedLeastSquares fit."""
+    """LinearRegression estimator over device-resident rows.
+
+    loss "squaredError" with solver "normal", or "auto" up to 4096 features:
+    the WeightedLeastSquares fit (one weighted syrk, a host solve).
+    loss "squaredError" otherwise: LBFGS / OWLQN over the device
+    LeastSquaresBlockAggregator on standardized features and label.
+    loss "huber": LBFGSB over the device HuberBlockAggregator, parameters
+    [coefficients, intercept, sigma], L2 only."""
 
     def __init__(self, maxIter: int = 100, regParam: float = 0.0, elasticNetParam: float = 0.0,
                  tol: float = 1e-6, fitIntercept: bool = True, standardization: bool = True,
-                 solver: str = "auto", loss: str = "squaredError"):
+                 solver: str = "auto", loss: str = "squaredError", epsilon: float = 1.35):
         if solver not in ("auto", "normal", "l-bfgs"):
             raise N.IllegalArgumentException(f"LinearRegression: unsupported solver {solver}")
         if loss not in ("squaredError", "huber"):
             raise N.IllegalArgumentException(f"LinearRegression: unsupported loss {loss}")
+        if not epsilon > 1.0:
+            raise N.IllegalArgumentException(
+                f"LinearRegression: epsilon given invalid value {epsilon}, must be > 1.0")
+        if loss == "huber" and elasticNetParam != 0.0:
+            raise N.IllegalArgumentException(
+                "requirement failed: LinearRegression with huber loss only supports L2 "
+                f"regularization, but got elasticNetParam = {elasticNetParam}.")
+        if loss == "huber" and solver == "normal":
+            raise N.IllegalArgumentException(
+                "requirement failed: LinearRegression with huber loss doesn't support normal "
+                "solver, please change solver to auto or l-bfgs.")
+        self.epsilon = float(epsilon)
         self.maxIter = int(maxIter)
         self.regParam = float(regParam)
         self.elasticNetParam = float(elasticNetParam)
@@ -388,20 +495,166 @@ class LinearRegression:
     def fit(self, X, y, weights=None) -> LinearRegressionModel:
         from .linalg import CSRRows
         numFeatures = X.numCols if isinstance(X, CSRRows) else int(X.shape[1])
-        if self.loss == "huber":
-            raise NotImplementedError(
-                "LinearRegression(loss='huber') is not implemented: it is the l-bfgs loop over "
-                "the device HuberBlockAggregator (optim.HuberBlockAggregator)")
-        if self.solver == "normal" or (self.solver == "auto" and numFeatures <= MAX_NUM_FEATURES):
+        if self.loss == "squaredError" and (
+                self.solver == "normal" or
+                (self.solver == "auto" and numFeatures <= MAX_NUM_FEATURES)):
             wls = WeightedLeastSquares(self.fitIntercept, self.regParam, self.elasticNetParam,
                                        standardizeFeatures=self.standardization,
                                        standardizeLabel=True, solverType="auto",
                                        maxIter=self.maxIter, tol=self.tol)
             m = wls.fit(X, y, weights)
-            return LinearRegressionModel(m.coefficients, m.intercept, 1.0, m.objectiveHistory,
-                                         m.diagInvAtWA)
-        raise NotImplementedError(
-            f"LinearRegression(solver='{self.solver}') with {numFeatures} features is not "
-            "implemented: it is the l-bfgs loop over the device LeastSquaresBlockAggregator "
-            "(optim.LeastSquaresBlockAggregator); only the normal-equation fit (solver "
-            f"'normal', or 'auto' up to {MAX_NUM_FEATURES} features) is")
+            model = LinearRegressionModel(m.coefficients, m.intercept, 1.0, m.objectiveHistory,
+                                          m.diagInvAtWA, self.fitIntercept)
+            # standard errors need the unregularized inverse
+            model._inference = self.regParam == 0.0
+            model._training = (X, y, weights, None)
+            return model
+        return self._fit_quasi_newton(X, y, weights, numFeatures)
+
+    def _fit_quasi_newton(self, X, y, weights, numFeatures):
+        """The summaries (features: the device summarizer; label: a one-column
+        one), then train_from_summary over the device aggregators."""
+        from . import optim
+        from .linalg import CSRRows
+        from .stat import SummarizerBuffer
+        if not isinstance(X, CSRRows) and not _torch().is_tensor(X):
+            # outside fit's contract (device rows); there is no host data pass
+            aggregator = "HuberBlockAggregator" if self.loss == "huber" \
+                else "LeastSquaresBlockAggregator"
+            raise NotImplementedError(
+                f"LinearRegression(loss='{self.loss}', solver='{self.solver}') with "
+                f"{numFeatures} features over host rows ({type(X).__name__}) is not "
+                f"implemented: the fit runs over the device {aggregator} "
+                f"(optim.{aggregator}), which takes an fp64 device tensor or linalg.CSRRows")
+        device = y.device
+        if isinstance(X, CSRRows):
+            block = optim.DeviceInstanceBlock(y, weights, rowptr=X.rowptr, colidx=X.colidx,
+                                              values=X.values, numFeatures=numFeatures)
+        else:
+            block = optim.DeviceInstanceBlock(y, weights, X=X.contiguous())
+        feat = SummarizerBuffer.of_block(block).allgather_merge()
+        lab = SummarizerBuffer.of_dense(y.reshape(-1, 1), weights).allgather_merge()
+        if feat.count <= 0:
+            raise N.IllegalArgumentException("requirement failed: Training dataset is empty.")
+        if not feat.weightSum > 0.0:
+            raise N.IllegalArgumentException("requirement failed: Sum of weights cannot be zero.")
+        if block.is_sparse:
+            # the layout the binary aggregators run on, once per fit
+            block.prepare(layout="tiles")
+
+        def make_cost(loss, fitIntercept, inverseStd, featuresMean, labelStd, labelMean, epsilon):
+            # raw rows: the aggregator sees unit inverseStd and the unscaled mean
+            ones = np.ones(numFeatures)
+            mean = np.asarray(featuresMean, dtype=np.float64) if fitIntercept else None
+            if loss == "huber":
+                scale = np.ones(numFeatures + (2 if fitIntercept else 1))
+                scale[:numFeatures] = inverseStd
+                make = lambda raw: optim.HuberBlockAggregator(  # noqa: E731
+                    ones, mean, fitIntercept, epsilon, raw, device=device)
+            else:
+                scale = inverseStd
+                make = lambda raw: optim.LeastSquaresBlockAggregator(  # noqa: E731
+                    ones, mean, fitIntercept, labelStd, labelMean, raw, device=device)
+            # kept as lastCost: its evaluations count the data passes
+            self.lastCost = BlockCost(block, make, scale)
+            return self.lastCost
+
+        yMean, yStd = float(lab.mean[0]), float(lab.std[0])
+        model = self.train_from_summary(numFeatures, feat.mean, feat.std, yMean, yStd,
+                                        feat.weightSum, make_cost)
+        model._training = (X, y, weights, yMean)
+        return model
+
+    def train_from_summary(self, numFeatures: int, featuresMean, featuresStd, yMean: float,
+                           yStd: float, weightSum: float, make_cost) -> LinearRegressionModel:
+        """The driver logic of the quasi-Newton fits once the summaries exist.
+        make_cost(loss, fitIntercept, inverseStd, featuresMean, labelStd,
+        labelMean, epsilon) returns a function: parameters of the SCALED
+        problem -> (loss, gradient) without the regularization term, i.e. one
+        pass of LeastSquaresBlockAggregator (labelStd, labelMean given, epsilon
+        None) or HuberBlockAggregator (epsilon given) over the standardized
+        rows."""
+        F = int(numFeatures)
+        featuresMean = np.asarray(featuresMean, dtype=np.float64)
+        featuresStd = np.asarray(featuresStd, dtype=np.float64)
+        yMean, yStd = float(yMean), float(yStd)
+        if not weightSum > 0.0:
+            raise N.IllegalArgumentException("requirement failed: Sum of weights cannot be zero.")
+        if not self.regParam >= 0.0:
+            raise N.IllegalArgumentException(
+                f"requirement failed: regParam cannot be negative: {self.regParam}")
+        if not 0.0 <= self.elasticNetParam <= 1.0:
+            raise N.IllegalArgumentException(
+                "requirement failed: elasticNetParam must be in [0, 1]: "
+                f"{self.elasticNetParam}")
+        inverseStd = _safe_div(1.0, featuresStd)
+        stdOf = None if self.standardization else featuresStd
+        if self.loss == "huber":
+            return self._train_huber(F, featuresMean, inverseStd, stdOf, make_cost)
+
+        if yStd == 0.0:
+            if self.fitIntercept or yMean == 0.0:
+                # a constant label: zero coefficients, the label as the intercept
+                return LinearRegressionModel(np.zeros(F), yMean, 1.0, [0.0],
+                                             fitIntercept=self.fitIntercept)
+            if self.regParam != 0.0:
+                raise N.IllegalArgumentException(
+                    "requirement failed: The standard deviation of the label is zero. Model "
+                    "cannot be regularized.")
+            yStd = abs(yMean)
+        effReg = self.regParam / yStd
+        effL1 = self.elasticNetParam * effReg
+        effL2 = (1.0 - self.elasticNetParam) * effReg
+        cost = make_cost("squaredError", self.fitIntercept, inverseStd, featuresMean, yStd, yMean,
+                         None)
+        regularization = _L2(effL2, F, stdOf) if effL2 != 0.0 else None
+        if effL1 != 0.0:
+            l1 = np.full(F, effL1) if self.standardization else _safe_div(effL1, featuresStd)
+            optimizer = optimize.OWLQN(self.maxIter, 10, l1, self.tol)
+        else:
+            optimizer = optimize.LBFGS(self.maxIter, 10, self.tol)
+        state, history = self._minimize(optimizer, cost, regularization, np.zeros(F))
+        coef = state.x * inverseStd * yStd
+        intercept = yMean - float(np.dot(coef, featuresMean)) if self.fitIntercept else 0.0
+        return LinearRegressionModel(coef, intercept, 1.0, history,
+                                     fitIntercept=self.fitIntercept)
+
+    def _train_huber(self, F, featuresMean, inverseStd, stdOf, make_cost):
+        fitIntercept = self.fitIntercept
+        dim = F + (2 if fitIntercept else 1)
+        cost = make_cost("huber", fitIntercept, inverseStd, featuresMean, None, None,
+                         self.epsilon)
+        regularization = _L2(self.regParam, F, stdOf) if self.regParam != 0.0 else None
+        lower = np.full(dim, -np.inf)
+        lower[dim - 1] = np.finfo(np.float64).tiny      # sigma > 0
+        optimizer = optimize.LBFGSB(lower, np.full(dim, np.inf), self.maxIter, 10, self.tol)
+        x0 = np.zeros(dim)
+        x0[dim - 1] = 1.0
+        # the aggregator centres whenever it fits an intercept: its intercept
+        # slot is the intercept of the centred rows (0 . scaledMean at x0)
+        state, history = self._minimize(optimizer, cost, regularization, x0)
+        sol = state.x
+        coef = sol[:F] * inverseStd
+        intercept = 0.0
+        if fitIntercept:
+            intercept = sol[F] - float(np.dot(coef, featuresMean))
+        return LinearRegressionModel(coef, intercept, float(sol[dim - 1]), history,
+                                     fitIntercept=fitIntercept)
+
+    def _minimize(self, optimizer, cost, regularization, x0):
+        def fn(x):
+            loss, grad = cost(x)
+            if regularization is not None:
+                rl, rg = regularization.calculate(x)
+                loss, grad = loss + rl, grad + rg
+            return loss, grad
+
+        history, state, last = [], None, None
+        for state in optimizer.iterations(fn, x0):
+            if state is not last:          # LBFGSB yields a failed state twice
+                history.append(state.adjustedValue)
+            last = state
+        if state is None:
+            raise RuntimeError(f"{type(optimizer).__name__} failed.")
+        self.lastState = state
+        return state, history

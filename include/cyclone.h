@@ -455,6 +455,33 @@ int cyc_glm_stats_csr_dev(cyc_glm_plan plan, const int64_t* rowptr, const int32_
                           const double* offset, const double* coef, double intercept,
                           int32_t project, double dispersion, double* sums, void* stream);
 
+/* ------------------------------------------- linear models: evaluate pass */
+/* One read of a shard's rows (dense row-major nrows x numFeatures, or CSR)
+ * for a fitted linear model: p_r = x_r . coef + intercept.
+ * predict: out[r] = p_r for every row.
+ * stats: with e_r = y_r - p_r, out (10 device doubles, overwritten) =
+ *   { sum w, sum w y, sum w y^2, sum w (y - center)^2, sum w e, sum w e^2,
+ *     sum w |e|, sum w (p - center)^2, min sqrt(w) e, max sqrt(w) e },
+ * the extrema over the rows with w > 0 (+inf, -inf if there is none); w may
+ * be NULL (all 1).  pred, if not NULL, receives every row's p_r in the same
+ * pass.  A row of weight 0 adds to no output.  With pred == NULL its features
+ * are not read; with pred they are read for pred[r] alone, so a NaN there
+ * reaches that one element and nothing else.  Per-wave partials folded in a
+ * fixed order, no floating-point atomics: two calls on the same input give
+ * the same bits. */
+int cyc_linreg_predict_dev(const double* X, int64_t nrows, int32_t numFeatures,
+                           const double* coef, double intercept, double* out, void* stream);
+int cyc_linreg_predict_csr_dev(const int64_t* rowptr, const int32_t* colidx, const double* vals,
+                               int64_t nrows, int32_t numFeatures, const double* coef,
+                               double intercept, double* out, void* stream);
+int cyc_linreg_stats_dev(const double* X, int64_t nrows, int32_t numFeatures, const double* y,
+                         const double* w, const double* coef, double intercept, double center,
+                         double* out, double* pred, void* stream);
+int cyc_linreg_stats_csr_dev(const int64_t* rowptr, const int32_t* colidx, const double* vals,
+                             int64_t nrows, int32_t numFeatures, const double* y,
+                             const double* w, const double* coef, double intercept,
+                             double center, double* out, double* pred, void* stream);
+
 /* ---------------------------------------------- logistic block aggregators */
 /* BinaryLogisticBlockAggregator.add (ml/optim/aggregator/
  * BinaryLogisticBlockAggregator.scala:81-145) and
