@@ -104,6 +104,9 @@ SIGNATURES = {
                                                     _vp]),
     "cyc_sparse_covariance_finalize_dev": (ctypes.c_int, [ctypes.c_int32, _vp, _i64, _vp, _vp,
                                                           _vp]),
+    "cyc_rowmatrix_multiply_dev": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "cyc_rowmatrix_multiply_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp,
+                                                      _vp]),
     "cyc_wls_plan_create": (ctypes.c_int, [_i32, ctypes.POINTER(_vp)]),
     "cyc_wls_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_wls_accumulate_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

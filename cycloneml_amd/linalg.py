@@ -7,12 +7,16 @@ SparseVector rows; rowptr int64, colidx int32, values fp64).  computeGramianMatr
 computeCovariance run the fp64-MFMA syrk of libcyclone and, when
 torch.distributed is initialised, merge the packed triangle with one
 all-reduce (the treeAggregate combOp U1 += U2, :149-157).  The eigensolve of
-PCA stays on the host (breeze svd on the driver in the reference, :501).
+PCA stays on the host (breeze svd on the driver in the reference, :501), and so
+does computeSVD's (:248-390, its local-LAPACK branch); multiply (:400-423) is
+the row-local fp64-MFMA product that applies their result to the rows.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -98,6 +102,33 @@ def triu_to_full(n, U, stream=None):
     G = torch.empty(n * n, dtype=torch.float64, device=U.device)
     N.check(N.load().cyc_triu_to_full_dev(int(n), N.ptr(U), N.ptr(G), N.stream_handle(stream)))
     return G.view(n, n).t()   # column-major storage -> G[i, j]
+
+
+SingularValueDecomposition = namedtuple("SingularValueDecomposition", ["U", "s", "V"])
+
+
+def svd_from_gramian(G, k: int, rCond: float = 1e-9):
+    """The host part of RowMatrix.computeSVD's local-LAPACK branch
+    (RowMatrix.scala:296-300, :334-357) as a function of the n x n Gramian:
+    (s, V) with s the leading singular values sqrt(eigenvalues of G), cut at
+    the first one below rCond * s[0] among the first k (sk = len(s) <= k; a
+    warning when sk < k), and V (n x sk) their right singular vectors, each
+    defined up to sign."""
+    G = np.asarray(G, dtype=np.float64)
+    n = G.shape[0]
+    if not (0 < k <= n):
+        raise N.IllegalArgumentException(
+            f"Requested k singular values but got k={k} and numCols={n}.")
+    u, sigmaSquares, _ = np.linalg.svd(G)
+    sigmas = np.sqrt(sigmaSquares)
+    threshold = rCond * sigmas[0]
+    sk = 0
+    while sk < k and sigmas[sk] >= threshold:
+        sk += 1
+    if sk < k:
+        warnings.warn(f"Requested {k} singular values but only found {sk} nonzeros.",
+                      RuntimeWarning, stacklevel=2)
+    return sigmas[:sk].copy(), u[:, :sk].copy()
 
 
 class RowMatrix:
@@ -425,3 +456,56 @@ class RowMatrix:
 
     def computePrincipalComponents(self, k: int):
         return self.computePrincipalComponentsAndExplainedVariance(k)[0]
+
+    def multiply(self, B, stream=None) -> "RowMatrix":
+        """RowMatrix.multiply (:400-423): the rows times a local n x k matrix
+        (numpy, or a device tensor), as a new RowMatrix over a dense nrows x k
+        device tensor.  Row-local: no collective.  fp64 MFMA for dense rows,
+        a gather of B's rows for CSR rows (absent entries skipped)."""
+        torch = _torch()
+        n = self.numCols()
+        if getattr(B, "ndim", 0) != 2:
+            raise N.IllegalArgumentException("B must be a matrix (n x k)")
+        if int(B.shape[0]) != n:
+            raise N.IllegalArgumentException(f"Dimension mismatch: {n} vs {int(B.shape[0])}")
+        k = int(B.shape[1])
+        # column-major values (DenseMatrix.values) on the rows' device
+        if isinstance(B, torch.Tensor):
+            Bv = B.to(device=self._device, dtype=torch.float64).t().contiguous()
+        else:
+            Bv = torch.from_numpy(np.ascontiguousarray(np.asarray(B, dtype=np.float64).T)) \
+                .to(self._device)
+        m = self._local_rows()
+        Y = torch.empty((m, k), dtype=torch.float64, device=self._device)
+        lib = N.load()
+        if self._sparse:
+            r = self.rows
+            N.check(lib.cyc_rowmatrix_multiply_csr_dev(
+                N.ptr(r.rowptr), N.ptr(r.colidx), N.ptr(r.values), m, n, N.ptr(Bv), k, N.ptr(Y),
+                N.stream_handle(stream)))
+        else:
+            X = self.rows if self.rows.is_contiguous() else self.rows.contiguous()
+            N.check(lib.cyc_rowmatrix_multiply_dev(N.ptr(X), m, n, N.ptr(Bv), k, N.ptr(Y),
+                                                   N.stream_handle(stream)))
+        return RowMatrix(Y, self._nRows, k)
+
+    def computeSVD(self, k: int, computeU: bool = False, rCond: float = 1e-9):
+        """RowMatrix.computeSVD (:248-390), its local-LAPACK branch: the
+        Gramian by the device syrk (merged over ranks), its eigendecomposition
+        on the host (brzSvd(G), :299), sigmas = sqrt, the rCond cut, and
+        U = A (V diag(1 / s)) by multiply.  Returns
+        SingularValueDecomposition(U, s, V): U a RowMatrix over this rank's
+        rows (None unless computeU), s a numpy vector of length sk <= k, V
+        numpy n x sk.  Singular vectors are defined up to sign.
+
+        The reference's ARPACK modes (local-eigs, dist-eigs; :287-295,
+        :301-332, chosen there for n >= 100 with small k or n > 15000) are not
+        restated: every k in (0, n] takes this branch, including k == n, which
+        the reference's dist-eigs mode would refuse (its require k < n)."""
+        n = self.numCols()
+        if not (0 < k <= n):
+            raise N.IllegalArgumentException(
+                f"Requested k singular values but got k={k} and numCols={n}.")
+        s, V = svd_from_gramian(self.computeGramianMatrix(), k, rCond)
+        U = self.multiply(V / s) if computeU else None
+        return SingularValueDecomposition(U, s, V)

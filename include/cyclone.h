@@ -347,6 +347,24 @@ int cyc_rowmatrix_dense_rows_dev(const double* X, const int64_t* rowptr, const d
  * mirrored (n x n column-major). */
 int cyc_sparse_covariance_finalize_dev(int32_t n, const double* U, int64_t m, const double* mean,
                                        double* G, void* stream);
+/* RowMatrix.multiply (:400-423), the pass behind computeSVD's U and
+ * PCAModel.transform:
+ * Y (nrows x k, row-major) = X (nrows x n, row-major) * B (n x k, column-major:
+ * Spark's DenseMatrix.values).  All pointers device, fp64.  Y must not overlap
+ * X or B.  Any nrows >= 0 (0: no launch), n >= 1, k >= 1, n k <= Int.MaxValue
+ * (DenseMatrix's array bound; CYC_ERR_INVALID_ARG otherwise).  Dense rows:
+ * fp64 MFMA over 64-column panels of B, one read of X per panel.  CSR rows
+ * (rowptr int64[nrows + 1], any base; colidx int32 validated as SparseVector
+ * indices): absent entries are skipped, as the reference's sparse dot skips
+ * them.  Each Y[i][l] is summed by one wave in a fixed order (no atomics, no
+ * split over the contraction): two calls on the same inputs give the same
+ * bits, and a NaN or Inf in a row of X or a column of B reaches only the
+ * outputs a per-element dot gives it. */
+int cyc_rowmatrix_multiply_dev(const double* X, int64_t nrows, int32_t n, const double* B,
+                               int32_t k, double* Y, void* stream);
+int cyc_rowmatrix_multiply_csr_dev(const int64_t* rowptr, const int32_t* colidx,
+                                   const double* vals, int64_t nrows, int32_t n, const double* B,
+                                   int32_t k, double* Y, void* stream);
 
 /* ------------------------------------------ WeightedLeastSquares moments */
 /* Replaces WeightedLeastSquares.Aggregator.add (ml/optim/
