@@ -4,8 +4,12 @@ orc_find_closest_stats_sparse, orc_kmeans_partition_sparse).
 
 Bar: assignments and per-point costs bit-exact (the norm-trick
 fastSquaredDistance of MLUtils.scala:533-576 is replayed in the reference's
-order); cluster sums / weights / cost within 1e-12 relative (fp64 atomics:
-order-free to rounding); centers as the oracle's update to 1e-12.
+order); cluster sums / weights / cost within 1e-12 relative (no atomics: a
+stable radix sort groups each entry's terms in row order and a deterministic
+reduce-by-key folds them, so only the fold's tree order differs from the
+reference's sequential one); centers bit-exact against the oracle's update
+fed the device's sums.  tests/test_kmeans_sparse_conformance.py holds the
+derived per-entry bound and the launch, tile and row-length edges.
 """
 import json
 import os
