@@ -2,8 +2,8 @@
 
 Mirrors mllib/clustering/KMeans.scala (the Lloyd loop :240-349 and its
 parameters) and KMeansModel; the per-partition body runs in libcyclone
-(cycloneml_amd/csrc/kmeans.hip: the plan and the C ABI; kmeans_i8.hip,
-kmeans_fp64.hip, kmeans_sums.hip, kmeans_sparse.hip, kmeans_cos.hip: the
+(cycloneml_amd/csrc/kmeans.hip: the plan and the C ABI; kmeans_i8.hip and
+its stages kmeans_i8_{rows,centers,cands,lists}.hip, kmeans_fp64.hip, kmeans_sums.hip, kmeans_sparse.hip, kmeans_cos.hip: the
 tiers' kernels).  Data stays resident in HBM: `run` takes a
 torch CUDA fp64 tensor of shape (n, d) -- one process per GPU holding its
 shard of the rows (the Spark partitions assigned to that GPU).  When

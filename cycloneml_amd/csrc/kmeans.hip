@@ -8,20 +8,21 @@
 // What a Euclidean Lloyd call (cyc_kmeans_accumulate_dev) runs, in order, all
 // device-resident on one stream:
 //   1. Center preparation (prep_all here; cyc::km8::centers_prepare_all,
-//      kmeans_i8.hip): the require(norm >= 0) check, computeStatistics
+//      kmeans_i8_centers.hip): the require(norm >= 0) check, computeStatistics
 //      (0.25*dist^2 packed upper + row minima, bit-exact), the transposed
 //      centers Ct (the fp64 MFMA B operand), the carried bounds' center drift
 //      and neighbourhoods, the i8 center image and the screens' zeroed
 //      counters, as three fused launches.  CYC_KMEANS_PREP=0, a row image of
 //      d > 256 and the other entry points run the same bodies as separate
 //      launches (require_enqueue, do_stats, bounds_prepare, do_assign).
-//   2. Carried bounds (bounds_* here; kernels in kmeans_i8.hip): with a row
+//   2. Carried bounds (bounds_* here; kernels in kmeans_i8_lists.hip, the
+//      re-check in kmeans_i8_cands.hip): with a row
 //      image, rows whose bounds of the last call still certify their center
 //      are kept; the others are listed for re-check or for the screens.
 //   3. i8 exact-integer screens over the row image (cyc::km8::screen,
 //      kmeans_i8.hip): one-limb pass and two-limb refinement, candidate
-//      pass, three-limb candidate tier; screen_setup here builds their
-//      arguments once per call.  Without a row image: the bf16x3 screen
+//      pass, three-limb candidate tier (kmeans_i8_cands.hip); screen_setup
+//      here builds their arguments once per call.  Without a row image: the bf16x3 screen
 //      (kmeans_fp64.hip) or none.
 //   4. fp64 MFMA screen (cyc::kmfp64::launch_assign, kmeans_fp64.hip) over
 //      the rows the screens before it queued, or over every row: a row whose
@@ -55,6 +56,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "kmeans_centers.hpp"
 #include "kmeans_i8.hpp"
 #include "kmeans_cos.hpp"
 #include "kmeans_fp64.hpp"
@@ -69,8 +71,15 @@ using cyc::kmsums::kMaxK;
 
 // --------------------------------------------------------------- switches
 // Every environment switch this file reads, with its default and when it is
-// read.  (CYC_KMEANS_PREP, CYC_KMEANS_RECHECK and CYC_KMEANS_SIDE are read in
-// kmeans_i8.hip, CYC_KMEANS_DUMP and CYCLONE_STRICT_PARITY in common.hpp.)
+// read.  (CYC_KMEANS_DUMP and CYCLONE_STRICT_PARITY are read in common.hpp;
+// the i8 screen's own switches, each through one accessor of kmeans_i8.hpp:
+//   CYC_KMEANS_PREP     on     kmeans_i8_centers.hip  prep_fused(); 0: the separate launches
+//   CYC_KMEANS_RECHECK  unset  kmeans_i8_lists.hip    recheck_two_phase(); 1: one-phase re-check
+//   CYC_KMEANS_SIDE     unset  kmeans_i8.hip          screen_side_stream(); 1: the three-limb
+//                                                     pass beside the candidate pass
+//   CYC_QUANT_PF        on     kmeans_i8_rows.hip     rows_quantize(); 0: the row-at-a-time
+//                                                     image kernel
+// all read once.)
 //   name                    default  read          meaning
 //   CYC_KMEANS_ASSIGN       unset    plan create   1/2/3: the screen tier of a plan without
 //                                                  a row image (test hook, Sizing::variant)
@@ -181,8 +190,8 @@ __global__ void k_center_transpose(const double* __restrict__ C, int k, int d, i
 }
 
 // kInfBits, the statistics' tile sizes and the bodies of the center kernels
-// below live in kmeans_i8.hpp (cyc::kmc): centers_prepare_all runs the same
-// bodies as jobs of its fused launches.
+// below live in kmeans_centers.hpp (cyc::kmc): centers_prepare_all
+// (kmeans_i8_centers.hip) runs the same bodies as jobs of its fused launches.
 using cyc::kmc::kInfBits;
 using cyc::kmc::kStT;
 using cyc::kmc::kStC;
@@ -526,18 +535,18 @@ int bounds_lists(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* xnorm, i
     // re-check the filter lists its state-1 rows there itself and the
     // re-check appends its failures)
     const bool two = k8::recheck_two_phase();
-    if ((rc = k8::bounds_filter((const int32_t*)rows->bAssign.ptr, (float2*)rows->bnd.ptr,
-                                bd.lnc, bd.state, xnorm, n, k, (const double*)rows->bDelta.ptr,
-                                bd.dp, bd.tmp, bd.bcount, (int32_t*)rows->bRc.ptr,
-                                (unsigned int*)rows->bRcCount.ptr,
-                                (unsigned long long*)rows->bRcCum.ptr,
-                                nbrOff() ? nullptr : (const double*)p->stats.ptr,
-                                (int32_t*)rows->bNbr.ptr, (float*)rows->bNbrR.ptr, st,
-                                two ? (int32_t*)rows->bTmp2.ptr : nullptr,
-                                two ? (unsigned int*)rows->bCount2.ptr : nullptr,
-                                two ? bd.list : nullptr, two ? bd.listCount : nullptr,
-                                two ? bd.cum : nullptr, nbrsReady)))
-      return rc;
+    k8::FilterArgs fa{(const int32_t*)rows->bAssign.ptr, xnorm, k,
+                      (const double*)rows->bDelta.ptr, (int32_t*)rows->bRc.ptr,
+                      (unsigned int*)rows->bRcCount.ptr, (unsigned long long*)rows->bRcCum.ptr};
+    fa.stats = nbrOff() ? nullptr : (const double*)p->stats.ptr;
+    fa.nbr = (int32_t*)rows->bNbr.ptr;
+    fa.nbrR = (float*)rows->bNbrR.ptr;
+    fa.nbrsReady = nbrsReady;
+    if (two) {
+      fa.tmp2 = (int32_t*)rows->bTmp2.ptr;
+      fa.bcount2 = (unsigned int*)rows->bCount2.ptr;
+    }
+    if ((rc = k8::bounds_filter(bd, fa, st))) return rc;
     bd.collected = two;
     if (!nbrOff()) {
       bd.nbr = (const int32_t*)rows->bNbr.ptr;
@@ -602,9 +611,12 @@ int stage_args(cyc_kmeans_plan p, int64_t n, bool useCa, cyc::km8::AppendStage& 
 
 // The i8 screens' optional arguments for one call: the candidate pass, the
 // one-limb pass + refinement and the append stage, each with whether this
-// call uses it.  Built once per call (screen_setup), read by prep_all for the
-// counters its fused launch zeroes and by the screen itself.
+// call uses it, and what every launch of the screen shares (call; its
+// xnorm, assign and st are the entry point's, set by do_assign / cos_assign).
+// Built once per call (screen_setup), read by prep_all for the counters its
+// fused launch zeroes and by the screen itself.
 struct ScreenSetup {
+  cyc::km8::ScreenCall call;
   cyc::km8::CandArgs ca;
   cyc::km8::RefineArgs ra;
   cyc::km8::AppendStage sg;
@@ -627,6 +639,10 @@ int screen_setup(cyc_kmeans_plan p, cyc_kmeans_rows rows, int64_t n, const doubl
       (!unit && (rc = refine_args(p, n, ss.useCa, ss.ra, ss.useRa))) ||
       (rc = stage_args(p, n, ss.useCa, ss.sg, ss.useSg)))
     return rc;
+  ss.call = cyc::km8::ScreenCall{rows->img.ptr, (const int2*)rows->meta.ptr, nullptr, n, p->d,
+                                 p->cb8.ptr, (const float*)p->cq8.ptr, (const double*)p->g8.ptr,
+                                 cnorm, (const cyc::km8::CenterParams*)p->prm8.ptr, p->ktp8,
+                                 nullptr, nullptr};
   return CYC_OK;
 }
 
@@ -683,13 +699,13 @@ int do_assign(cyc_kmeans_plan p, const AssignCall& a, const ScreenSetup& ss, hip
                                         (cyc::km8::CenterParams*)p->prm8.ptr,
                                         (double*)p->scr8.ptr, st)))
       return rc;
-    if ((rc = cyc::km8::screen(a.rows->img.ptr, (const int2*)a.rows->meta.ptr, xnorm, n, p->d,
-                               p->cb8.ptr, (const float*)p->cq8.ptr, (const double*)p->g8.ptr,
-                               cnorm, (const cyc::km8::CenterParams*)p->prm8.ptr, p->ktp8,
-                               a.assign, (int32_t*)p->list3.ptr,
-                               (unsigned int*)p->list3Count.ptr, slowList,
-                               (unsigned int*)p->list8Count.ptr, st, ss.cand(), ss.refine(),
-                               ss.stage(), a.bounds, a.prepared)))
+    cyc::km8::ScreenCall sc = ss.call;
+    sc.xnorm = xnorm;
+    sc.assign = a.assign;
+    sc.st = st;
+    if ((rc = cyc::km8::screen(sc, (int32_t*)p->list3.ptr, (unsigned int*)p->list3Count.ptr,
+                               slowList, (unsigned int*)p->list8Count.ptr, ss.cand(),
+                               ss.refine(), ss.stage(), a.bounds, a.prepared)))
       return rc;
     rowList = (const int32_t*)p->list3.ptr;
     rowCount = (const unsigned int*)p->list3Count.ptr;
@@ -942,16 +958,16 @@ int cos_assign(cyc_kmeans_plan p, const double* X, const double* xnorm, cyc_kmea
     CYC_HIP(hipMemsetAsync(count, 0, sizeof(unsigned int), st));
     ScreenSetup ss;
     if ((rc = screen_setup(p, rows, n, X, xnorm, V, Vn, true, ss))) return rc;
+    cyc::km8::ScreenCall sc = ss.call;
+    sc.xnorm = (const double*)rows->unorm.ptr;   // the unit directions' norms
+    sc.assign = assign;
+    sc.st = st;
     if ((rc = cyc::km8::centers_prepare(V, Vn, p->k, p->d, p->ktp8, p->cb8.ptr,
                                         (float*)p->cq8.ptr, (double*)p->g8.ptr,
                                         (cyc::km8::CenterParams*)p->prm8.ptr,
                                         (double*)p->scr8.ptr, st)) ||
-        (rc = cyc::km8::screen(rows->img.ptr, (const int2*)rows->meta.ptr,
-                               (const double*)rows->unorm.ptr, n, p->d, p->cb8.ptr,
-                               (const float*)p->cq8.ptr, (const double*)p->g8.ptr, Vn,
-                               (const cyc::km8::CenterParams*)p->prm8.ptr, p->ktp8, assign, list,
-                               count, (int32_t*)p->slowList.ptr,
-                               (unsigned int*)p->list8Count.ptr, st, ss.cand(), nullptr,
+        (rc = cyc::km8::screen(sc, list, count, (int32_t*)p->slowList.ptr,
+                               (unsigned int*)p->list8Count.ptr, ss.cand(), nullptr,
                                ss.stage())))
       return rc;
   } else if ((rc = cyc::kmcos::list_all(list, count, n, st))) {

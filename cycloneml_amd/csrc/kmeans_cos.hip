@@ -5,7 +5,8 @@
 //   statistics   k_cos_stats_pairs / k_cos_stats_diag: 1 - sqrt(1 - d/2) per
 //                center pair, d = 1 - dot(ci, cj) / |ci| / |cj|, the dot a
 //                sequential ddot (bit-exact);
-//   assignment   the exact-integer i8 screen of kmeans_i8.hip run on UNIT
+//   assignment   the exact-integer i8 screen (kmeans_i8.hpp; kernels in
+//                kmeans_i8.hip and kmeans_i8_*.hip) run on UNIT
 //                directions (x / |x| rows, c / |c| centers): for unit vectors
 //                |u - v|^2 = 2 (1 - cos), so the Euclidean winner the screen
 //                certifies is the cosine winner, with the screen's margin

@@ -1,6 +1,7 @@
 // kmeans_fp64.hip -- the dense KMeans screens that decide in fp64, and the
 // exact tier, on gfx950 (MI355X): the tiers of a Euclidean Lloyd call behind
-// the i8 screens of kmeans_i8.hip (kmeans.hip has the order of the tiers).
+// the i8 screens of kmeans_i8.hip and kmeans_i8_cands.hip (kmeans.hip has the
+// order of the tiers).
 //
 //   k_kmeans_assign / k_kmeans_assign2   fp64 MFMA (v_mfma_f64_16x16x4f64)
 //       screen of |x|^2 + |c|^2 - 2 x.c for an LDS tile of rows against every

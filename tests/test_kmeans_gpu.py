@@ -683,7 +683,7 @@ def test_one_limb_refinement_lloyd(cuda, n, d, k, sep, dup):
 @pytest.mark.parametrize("cands3", ["1", "0"])
 def test_three_limb_candidate_tier(cuda, monkeypatch, n, d, k, cands3):
     """Rows the two-limb tiers hand to the candidate pass first meet the
-    three-limb candidate tier (kmeans_i8.hip k_screen_cands3: exact integer
+    three-limb candidate tier (kmeans_i8_cands.hip k_screen_cands3: exact integer
     limb products over the row's <= 6 candidates, the three-limb pass's
     bounds); the rows it cannot certify go on to the fp64 candidate pass.
     Close clusters with near-duplicate centers (near ties); d = 200 (16
@@ -840,7 +840,7 @@ def _lloyd_run(Xd, Cd0, cuda, iters, bounds, hook=None):
                                        (150_000, 200, 300, 1.5)])
 def test_carried_bounds_bitwise(cuda, n, d, k, sep):
     """Carried (Hamerly) bounds across the Lloyd iterations of one fit
-    (kmeans_i8.hpp Bounds): twelve iterations with the bounds on give the
+    (kmeans_i8.hpp Bounds, kmeans_i8_lists.hip): twelve iterations with the bounds on give the
     SAME bits as with them off -- every row's assignment and cost, the
     cluster sums, weights and cost -- and the last iteration equals the
     restatement (KMeans.scala:275-334 on the same centers) for every row; the
@@ -1261,7 +1261,7 @@ print(" ".join(f"{x}:{y}" for x, y in info))
 
 @pytest.mark.parametrize("d,k,n", [(256, 300, 80000), (64, 200, 60000)])
 def test_recheck_forms_identical(cuda, d, k, n):
-    """The two-phase re-check (k_recheck, the default) against the one-phase
+    """The two-phase re-check (kmeans_i8_cands.hip k_recheck, the default) against the one-phase
     k_screen_cands3<.., true> (CYC_KMEANS_RECHECK=1): the same centers each
     iteration give the same assignments, iteration by iteration, and the
     same carried-state traffic.  The counters are compared within 0.5 %:

@@ -18,7 +18,7 @@ else
   base=$(basename "$SRC" .hip)
   in=$base.hip
 fi
-extra=""; [ "$base" = kmeans_i8 ] && extra="-fno-slp-vectorize"
+extra=""; [[ "$base" == kmeans_i8* ]] && extra="-fno-slp-vectorize"   # as the Makefile
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I. $extra $DEFS -c -o /tmp/variant_$NAME.o "$in"
 objs=$(ls build/*.o | grep -v -e "build/$base.o" -e "build/blas.o")
 mkdir -p ../../tools/bin

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """How many rows could carried bounds keep?  One fit on bench.py's KMeans
 rows (config 2, setInitialModel = rows 0..1023) through KMeansPlan.accumulate
-with the library's carried bounds (kmeans_i8.hpp Bounds); per iteration:
+with the library's carried bounds (kmeans_i8.hpp Bounds, the filter in
+kmeans_i8_lists.hip); per iteration:
   lib_screened   rows the library screened (cyc_kmeans_rows_bounds_info)
   exact_kept     on a fixed sample (every 50th row), the fraction EXACT
                  Hamerly bounds would keep: ub = |x - c_w|, lb = the second

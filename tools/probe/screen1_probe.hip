@@ -81,11 +81,15 @@ int main(int argc, char** argv) {
   auto launch = [&]() {
     CK(hipMemsetAsync(dCnt, 0, cntBytes, 0));
     CK(hipMemsetAsync(dCc, 0, cntBytes, 0));
+    // (ScreenCall::ktp counts 16-center tiles; the pass reads its constants
+    // at pass_consts(2 ktp, 1) of cq / g)
+    const cyc::km8::ScreenCall sc{dImg, (const int2*)dMeta, (const double*)dXn, n, d, dCb,
+                                  (const float*)dCq, (const double*)dG, (const double*)dCn,
+                                  (const cyc::km8::CenterParams*)dP, 2 * ktp, (int32_t*)dAssign,
+                                  0};
     return cyc::km8::launch_screen32<8, PROBE_W, 1, false>(
-        dImg, (const int2*)dMeta, (const double*)dXn, n, d, dCb, (const float*)dCq,
-        (const double*)dG, (const double*)dCn, (const cyc::km8::CenterParams*)dP, ktp, nullptr,
-        nullptr, (int32_t*)dAssign, (int32_t*)dList, (unsigned int*)dCnt, 0, (int32_t*)dCr,
-        (int32_t*)dC1, (unsigned int*)dCc, scap);
+        sc, nullptr, nullptr, {(int32_t*)dList, (unsigned int*)dCnt},
+        {(int32_t*)dCr, (unsigned int*)dCc, (int32_t*)dC1}, scap);
   };
   for (int i = 0; i < 3; ++i)
     if (launch()) return 1;
