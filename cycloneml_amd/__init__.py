@@ -7,6 +7,10 @@ include/cyclone.h); these modules mirror the reference's Scala interfaces.
 __version__ = "0.1.0"
 
 from . import _native  # noqa: F401  (loads nothing until first use)
+from .classification import (  # noqa: F401
+    MultilayerPerceptronClassificationModel,
+    MultilayerPerceptronClassifier,
+)
 from .feature import PCA, PCAModel  # noqa: F401
 from .glm import (  # noqa: F401
     GeneralizedLinearRegression,

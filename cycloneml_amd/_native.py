@@ -179,6 +179,11 @@ SIGNATURES = {
     "cyc_multinomial_logistic_add_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cyc_softmax_exp_dev": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    "cyc_mlp_plan_create": (ctypes.c_int, [_pi32, ctypes.c_int, ctypes.c_int, _i64,
+                                           ctypes.POINTER(_vp)]),
+    "cyc_mlp_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_mlp_loss_grad_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "cyc_mlp_forward_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "cyc_csc_features": (_i32, [_vp]),
     "cyc_tiles_create": (ctypes.c_int, [_i32, _i64, _i64, ctypes.POINTER(_vp)]),
     "cyc_tiles_append_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),

@@ -494,3 +494,161 @@ class _DeviceCost:
         agg.allreduce()
         self.evaluations += 1
         return agg.loss, agg.gradient * self.scale
+
+
+# -- MultilayerPerceptronClassifier ---------------------------------------------
+
+class MultilayerPerceptronClassificationTrainingSummary:
+    """objectiveHistory: the objective at every optimizer state, the initial
+    one included; totalIterations = len(objectiveHistory) - 1."""
+
+    def __init__(self, objectiveHistory):
+        self.objectiveHistory = np.asarray(objectiveHistory, dtype=np.float64)
+
+    @property
+    def totalIterations(self) -> int:
+        return max(len(self.objectiveHistory) - 1, 0)
+
+
+class MultilayerPerceptronClassificationModel:
+    """ml/classification/MultilayerPerceptronClassifier.scala:273-330: the
+    layers and the flat weights (cycloneml_amd.ann); predictions run the
+    device forward pass over fp64 device rows and stay on the device."""
+
+    def __init__(self, layers, weights, summary=None):
+        from . import ann
+        self.layers = ann.check_layers(layers)
+        self.weights = np.array(weights, dtype=np.float64).ravel()
+        if self.weights.size != ann.weight_length(self.layers):
+            raise N.IllegalArgumentException(
+                f"requirement failed: topology {self.layers} takes "
+                f"{ann.weight_length(self.layers)} weights but got {self.weights.size}")
+        self.summary = summary
+        self._plan = None
+        self._wdev = None
+
+    @property
+    def numFeatures(self) -> int:
+        return self.layers[0]
+
+    @property
+    def numClasses(self) -> int:
+        return self.layers[-1]
+
+    def save(self, path, overwrite=False):
+        from . import persist
+        persist.save_mlp_model(self, path, getattr(self, "uid", None), overwrite=overwrite)
+
+    @staticmethod
+    def load(path) -> "MultilayerPerceptronClassificationModel":
+        from . import persist
+        return persist.load_mlp_model(path)
+
+    def _forward(self, X, **which):
+        import torch
+        from . import ann
+        if self._plan is None:
+            self._plan = ann.MLPPlan(self.layers)
+        if self._wdev is None or self._wdev.device != X.device:
+            self._wdev = torch.from_numpy(self.weights).to(X.device)
+        return self._plan.forward(X, self._wdev, **which)
+
+    def predictRaw(self, X):
+        """z_L of every row (n x numClasses, device)."""
+        return self._forward(X, raw=True)[0]
+
+    def predictProbability(self, X):
+        """softmax(z_L) of every row (n x numClasses, device)."""
+        return self._forward(X, prob=True)[1]
+
+    def predict(self, X):
+        """argmax of the probabilities as fp64 (Vectors.argmax: the lowest
+        index on ties), device."""
+        return self._forward(X, pred=True)[2]
+
+
+class MultilayerPerceptronClassifier:
+    """MultilayerPerceptronClassifier.train (:177-252) with solver "l-bfgs":
+    breeze LBFGS(maxIter, 10, tol) (mllib/optimization/LBFGS.scala) over the
+    DataStacker objective of cycloneml_amd.ann, one device loss + gradient
+    pass and one all-reduce per evaluation.  solver "gd" is not provided."""
+
+    def __init__(self, layers, blockSize: int = 128, maxIter: int = 100, tol: float = 1e-6,
+                 seed: Optional[int] = None, solver: str = "l-bfgs", initialWeights=None,
+                 stepSize: float = 0.03):
+        from . import ann
+        self.layers = ann.check_layers(layers)
+        if int(blockSize) <= 0:
+            raise N.IllegalArgumentException(f"blockSize given invalid value {blockSize}")
+        if solver == "gd":
+            raise N.IllegalArgumentException(
+                'solver "gd" is not provided by this build; use "l-bfgs"')
+        if solver != "l-bfgs":
+            raise N.IllegalArgumentException(f"solver given invalid value {solver}")
+        if int(maxIter) < 0:
+            raise N.IllegalArgumentException(f"maxIter given invalid value {maxIter}")
+        if not tol >= 0:
+            raise N.IllegalArgumentException(f"tol given invalid value {tol}")
+        if not stepSize > 0:
+            raise N.IllegalArgumentException(f"stepSize given invalid value {stepSize}")
+        self.blockSize = int(blockSize)
+        self.maxIter = int(maxIter)
+        self.tol = float(tol)
+        self.seed = ann.DEFAULT_SEED if seed is None else int(seed)
+        self.solver = solver
+        self.stepSize = float(stepSize)
+        self.initialWeights = None
+        if initialWeights is not None:
+            self.initialWeights = np.array(initialWeights, dtype=np.float64).ravel()
+            if self.initialWeights.size != ann.weight_length(self.layers):
+                raise N.IllegalArgumentException(
+                    f"requirement failed: topology {self.layers} takes "
+                    f"{ann.weight_length(self.layers)} weights but initialWeights has "
+                    f"{self.initialWeights.size}")
+
+    def fit(self, X, y) -> MultilayerPerceptronClassificationModel:
+        """X: this rank's dense fp64 device rows (n x layers[0]); y: its labels
+        (device, class indices).  With several ranks every rank calls fit."""
+        import torch
+        from . import ann, parallel
+        from .linalg import CSRRows
+        if isinstance(X, CSRRows):
+            raise N.IllegalArgumentException(
+                "MultilayerPerceptronClassifier takes dense rows; CSR rows are not supported")
+        if not torch.is_tensor(X) or X.dim() != 2:
+            raise N.IllegalArgumentException(
+                "requirement failed: rows must be an fp64 device tensor (n x layers[0])")
+        if int(X.shape[1]) != self.layers[0]:
+            raise N.IllegalArgumentException(
+                f"requirement failed: the rows have {int(X.shape[1])} features but the input "
+                f"layer has {self.layers[0]}")
+        X = X.contiguous()
+        y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
+        n = int(X.shape[0])
+        nw = ann.weight_length(self.layers)
+        init = self.initialWeights if self.initialWeights is not None \
+            else ann.initial_weights(self.layers, self.seed)
+        # the blocks of all ranks, once
+        blocks = torch.tensor([float((n + self.blockSize - 1) // self.blockSize)],
+                              dtype=torch.float64, device=X.device)
+        parallel.allreduce_(blocks)
+        totalBlocks = int(blocks.item())
+        if totalBlocks < 1:
+            raise N.IllegalArgumentException("requirement failed: the training set is empty")
+        plan = ann.MLPPlan(self.layers, self.blockSize)
+        try:
+            def cost(w):
+                wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(X.device)
+                buf = torch.zeros(nw + 1, dtype=torch.float64, device=X.device)
+                plan.loss_grad(X, y, wd, totalBlocks, buf[:nw], buf[nw:])
+                parallel.allreduce_(buf)       # [grad, loss], the treeAggregate merge
+                host = buf.cpu().numpy()
+                return float(host[nw]), host[:nw].copy()
+
+            history, state = [], None
+            for state in optimize.LBFGS(self.maxIter, 10, self.tol).iterations(cost, init):
+                history.append(state.value)
+        finally:
+            plan.close()
+        summary = MultilayerPerceptronClassificationTrainingSummary(history)
+        return MultilayerPerceptronClassificationModel(self.layers, state.x, summary)

@@ -11,7 +11,11 @@ trained here loads in Spark (and back):
     (ml/util/ReadWrite.scala:422-451: class, timestamp, sparkVersion, uid,
     paramMap, defaultParamMap); data/ = one parquet row Data(numClasses,
     numFeatures, interceptVector: ml Vector, coefficientMatrix: Matrix,
-    isMultinomial).
+    isMultinomial);
+  - ml MultilayerPerceptronClassificationModel (ml/classification/
+    MultilayerPerceptronClassifier.scala): `layers` in the metadata's paramMap
+    and data/ = one parquet row Data(weights: ml Vector) (Spark 3); the reader
+    also takes the pre-3.0 row Data(layers: Array[Int], weights).
 Vectors and matrices use the UDT struct encodings (ml/linalg/VectorUDT.scala,
 MatrixUDT.scala:30-70, mllib/linalg/Vectors.scala:271-280): type 1 = dense
 (values; matrices also numRows/numCols/isTransposed), type 0 = sparse.
@@ -323,6 +327,59 @@ def load_logistic_model(path):
     m.uid = meta.get("uid")
     m.params = dict(meta.get("defaultParamMap", {}), **meta.get("paramMap", {}))
     m.fitIntercept = bool(m.params.get("fitIntercept", True))
+    return m
+
+
+# -- ml MultilayerPerceptronClassificationModel ---------------------------------
+
+MLP_CLASS = "org.apache.spark.ml.classification.MultilayerPerceptronClassificationModel"
+
+_MLP_DEFAULTS = {"featuresCol": "features", "labelCol": "label", "predictionCol": "prediction",
+                 "rawPredictionCol": "rawPrediction", "probabilityCol": "probability",
+                 "maxIter": 100, "tol": 1e-6, "blockSize": 128, "solver": "l-bfgs",
+                 "stepSize": 0.03}
+
+
+def save_mlp_model(model, path, uid=None, overwrite=False):
+    """MultilayerPerceptronClassificationModelWriter.saveImpl (Spark 3:
+    `layers` is a param of the model, in the metadata's paramMap; data/ = one
+    parquet row Data(weights: ml Vector))."""
+    pa, _ = _pa()
+    _check_new_path(path, overwrite)
+    meta = {"class": MLP_CLASS, "timestamp": int(time.time() * 1000),
+            "sparkVersion": SPARK_VERSION,
+            "uid": uid or f"mlpc_{uuid.uuid4().hex[:12]}",
+            "paramMap": {"layers": [int(n) for n in model.layers]},
+            "defaultParamMap": dict(_MLP_DEFAULTS)}
+    _write_text(os.path.join(path, "metadata"), json.dumps(meta, separators=(",", ":")))
+    fields = [pa.field("weights", _arrow_vector())]
+    spark = [_field("weights", _udt("vector"))]
+    _write_parquet(os.path.join(path, "data"), fields, spark,
+                   [{"weights": encode_dense_vector(model.weights)}])
+
+
+def load_mlp_model(path):
+    """MultilayerPerceptronClassificationModelReader.load: Spark >= 3.0 reads
+    Data(weights) and takes `layers` from the metadata; earlier releases
+    wrote the row Data(layers: Array[Int], weights: Vector)."""
+    from .classification import MultilayerPerceptronClassificationModel
+    meta = json.loads(_read_text(os.path.join(path, "metadata")))
+    if meta.get("class") != MLP_CLASS:
+        raise ValueError(f"requirement failed: Error loading metadata: Expected class name "
+                         f"{MLP_CLASS} but found class name {meta.get('class')}")
+    rows = _read_parquet_rows(os.path.join(path, "data"))
+    if len(rows) != 1:
+        raise ValueError("expected one data row")
+    r = rows[0]
+    if r.get("layers") is not None:
+        layers = [int(n) for n in r["layers"]]
+    else:
+        params = dict(meta.get("defaultParamMap", {}), **meta.get("paramMap", {}))
+        if "layers" not in params:
+            raise ValueError("the model's metadata holds no `layers` param")
+        layers = [int(n) for n in params["layers"]]
+    m = MultilayerPerceptronClassificationModel(layers, decode_vector(r["weights"]))
+    m.uid = meta.get("uid")
     return m
 
 

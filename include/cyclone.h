@@ -687,6 +687,44 @@ int cyc_multinomial_logistic_add_csr_dev(cyc_logistic_plan plan, const int64_t* 
  * testable against the host libm. */
 int cyc_softmax_exp_dev(const double* x, int64_t n, double* out, void* stream);
 
+/* ---------------------------------------- MultilayerPerceptronClassifier */
+/* The feed-forward network of ml/ann/Layer.scala (FeedForwardTopology
+ * .multiLayerPerceptron with softmaxOnTop): layers = [n_0 .. n_L], L =
+ * nlayers - 1 >= 1, every n_l in 1..4096; affine layers, a sigmoid after
+ * each but the last, softmax with cross-entropy on top.  The weights are one
+ * flat fp64 device array of sum n_l (n_{l-1} + 1) doubles: for l = 1..L, W_l
+ * (column-major n_l x n_{l-1}, W_l[o, i] at i n_l + o), then b_l.  X is
+ * dense row-major nrows x n_0, labels fp64 class indices.
+ *
+ * Rows are evaluated in chunks of chunkRows (0: as many as keep the plan's
+ * workspace of 2 chunkRows sum n_l doubles under 1 GiB); the plan owns the
+ * workspace and keeps it between calls.
+ *
+ * cyc_mlp_loss_grad_dev ADDS one shard's share of the DataStacker objective:
+ * the shard's rows are cut into blocks of blockSize (the last may be
+ * shorter), row i of block b (S_b rows) weighs s_i = 1 / (S_b totalBlocks),
+ * totalBlocks = the blocks of all shards; *loss += sum s_i (-log p_i[y_i]),
+ * grad (the weights' layout) += sum s_i dl_i/dw.  Only the target class's
+ * term of the cross-entropy is taken (the reference's sum over all classes
+ * gives NaN once a non-target probability underflows).  A label that is not
+ * an integer in [0, n_L) fails the call (CYC_ERR_INVALID_ARG; the call
+ * synchronizes the stream to read the flag, and grad / loss are then
+ * undefined).  No atomics: two calls on the same inputs add the same bits.
+ *
+ * cyc_mlp_forward_dev: raw (nrows x n_L, z_L), prob (softmax of z_L), pred
+ * (nrows; the argmax of prob as fp64, the lowest index on ties); any of the
+ * three may be NULL, not all. */
+typedef struct cyc_mlp_plan_s* cyc_mlp_plan;
+
+int cyc_mlp_plan_create(const int32_t* layers, int nlayers, int blockSize, int64_t chunkRows,
+                        cyc_mlp_plan* plan);
+int cyc_mlp_plan_destroy(cyc_mlp_plan plan);
+int cyc_mlp_loss_grad_dev(cyc_mlp_plan plan, const double* X, const double* labels, int64_t nrows,
+                          const double* weights, int64_t totalBlocks, double* grad, double* loss,
+                          void* stream);
+int cyc_mlp_forward_dev(cyc_mlp_plan plan, const double* X, int64_t nrows, const double* weights,
+                        double* raw, double* prob, double* pred, void* stream);
+
 /* ------------------------------------------------ summarizer pre-pass */
 /* The first pass of LogisticRegression.train (LogisticRegression.scala:
  * 511-516, Summarizer.getClassificationSummarizers, ml/stat/Summarizer.scala:
