@@ -12,6 +12,12 @@ from .classification import (  # noqa: F401
     MultilayerPerceptronClassifier,
 )
 from .feature import PCA, PCAModel  # noqa: F401
+from .gmm import (  # noqa: F401
+    GaussianMixture,
+    GaussianMixtureModel,
+    GMMPlan,
+    MultivariateGaussian,
+)
 from .glm import (  # noqa: F401
     GeneralizedLinearRegression,
     GeneralizedLinearRegressionModel,

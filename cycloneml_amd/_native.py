@@ -184,6 +184,12 @@ SIGNATURES = {
     "cyc_mlp_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_mlp_loss_grad_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "cyc_mlp_forward_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_gmm_plan_create": (ctypes.c_int, [_i32, _i32, _i64, ctypes.POINTER(_vp)]),
+    "cyc_gmm_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_gmm_set_model_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_gmm_accumulate_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "cyc_gmm_mstep_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "cyc_gmm_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "cyc_csc_features": (_i32, [_vp]),
     "cyc_tiles_create": (ctypes.c_int, [_i32, _i64, _i64, ctypes.POINTER(_vp)]),
     "cyc_tiles_append_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),

@@ -21,6 +21,13 @@ import numpy as np
 
 from . import _native as N
 from . import parallel
+# ml.clustering.GaussianMixture lives in gmm.py; its names belong here too
+from .gmm import (  # noqa: F401
+    GaussianMixture,
+    GaussianMixtureModel,
+    GMMPlan,
+    MultivariateGaussian,
+)
 
 
 def _torch():

@@ -725,6 +725,53 @@ int cyc_mlp_loss_grad_dev(cyc_mlp_plan plan, const double* X, const double* labe
 int cyc_mlp_forward_dev(cyc_mlp_plan plan, const double* X, int64_t nrows, const double* weights,
                         double* raw, double* prob, double* pred, void* stream);
 
+/* ------------------------------------------------------- GaussianMixture */
+/* The E step and the sufficient statistics of ml/clustering/
+ * GaussianMixture.scala (ExpectationAggregator.add) over dense row-major
+ * fp64 rows (nrows x numFeatures), 1 <= numFeatures <= 1024, k >= 1.
+ *
+ * Model (cyc_gmm_set_model_dev, all device fp64): weights (k), means (k x
+ * numFeatures, row-major), rootSigmaInv (k matrices numFeatures x
+ * numFeatures, row-major: A_j[c, f] at (j d + c) d + f) and u (k) with u_j =
+ * -0.5 (d log 2 pi + logPseudoDet_j), the constants of ml/stat/distribution/
+ * MultivariateGaussian.scala.  logpdf_j(x) = u_j - 0.5 |A_j (x - mu_j)|^2; the
+ * mean is subtracted before the product.  The plan keeps its own copy.
+ *
+ * Per row i of weight w_i (NULL: all 1): p_ij = EPSILON + weights_j
+ * exp(logpdf_j(x_i)), s_i = sum_j p_ij, r_ij = w_i p_ij / s_i, EPSILON =
+ * 2^-52.  sums is 1 + k + k d + k d(d+1)/2 doubles, [ll | W | M | S]: ll =
+ * sum_i w_i log s_i, W_j = sum_i r_ij, M_j (d) = sum_i r_ij x_i, S_j the
+ * packed upper triangle (column-major, S_j[b(b+1)/2 + a], a <= b) of sum_i
+ * r_ij x_i x_i^T.  cyc_gmm_accumulate_dev ADDS the rows' share; buffers of
+ * several calls (or ranks) merge by addition.  Rows of weight 0 contribute
+ * nothing, whatever their features hold.  A negative or NaN weight fails the
+ * call with "requirement failed: illegal weight value ..." (the call
+ * synchronizes the stream to read the flag; sums is then undefined).
+ *
+ * cyc_gmm_mstep_dev ADDS W, M and S alone from caller-supplied
+ * responsibilities R (nrows x k, row-major); sums[0] is not touched.
+ *
+ * cyc_gmm_predict_dev: prob (nrows x k, p_ij / s_i at unit row weight),
+ * label (nrows int32, the argmax of prob, the lowest index on ties), logpdf
+ * (nrows x k, logpdf_j(x_i)); any of the three may be NULL, not all.
+ *
+ * Rows go through in chunks of chunkRows (0: as many as keep the plan's r
+ * workspace of chunkRows k doubles under 1 GiB).  fp64 MFMA, fixed-order
+ * reductions, no atomics on doubles: two calls on the same inputs give the
+ * same bits. */
+typedef struct cyc_gmm_plan_s* cyc_gmm_plan;
+
+int cyc_gmm_plan_create(int32_t k, int32_t numFeatures, int64_t chunkRows, cyc_gmm_plan* plan);
+int cyc_gmm_plan_destroy(cyc_gmm_plan plan);
+int cyc_gmm_set_model_dev(cyc_gmm_plan plan, const double* weights, const double* means,
+                          const double* rootSigmaInv, const double* u, void* stream);
+int cyc_gmm_accumulate_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, const double* w,
+                           double* sums, void* stream);
+int cyc_gmm_mstep_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, const double* R,
+                      double* sums, void* stream);
+int cyc_gmm_predict_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, double* prob,
+                        int32_t* label, double* logpdf, void* stream);
+
 /* ------------------------------------------------ summarizer pre-pass */
 /* The first pass of LogisticRegression.train (LogisticRegression.scala:
  * 511-516, Summarizer.getClassificationSummarizers, ml/stat/Summarizer.scala:
