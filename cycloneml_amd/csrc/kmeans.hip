@@ -308,7 +308,7 @@ struct cyc_kmeans_plan_s {
   // cosine: unit center directions for the screen, their norms, computed
   // center norms (statistics without given norms)
   cyc::DeviceBuffer cosV, cosVn, cosCn;
-  bool dense_ok = true;     // d fits the LDS-resident dense assign kernels (d <= 1240)
+  bool dense_ok = true;     // d fits the LDS-resident dense assign kernels (d <= 1216)
   cyc::kmfp64::Sizing fp;   // the fp64 / bf16x3 screens' tiles and constants (kmeans_fp64.hpp)
   int64_t lastTier2 = 0;    // rows the bf16 screen queued (last counted call)
   int64_t lastExact = 0;    // rows the fp64 screen queued (last counted call)
@@ -1033,7 +1033,7 @@ int cyc_kmeans_plan_create(int32_t d, int32_t k, int64_t max_rows, cyc_kmeans_pl
   p->d = d;
   p->k = k;
   p->fp = cyc::kmfp64::sizing(d, k, sw_assign_variant());
-  // d > 1240: no LDS-resident dense assign; the plan still serves sparse rows
+  // d > 1216: no LDS-resident dense assign; the plan still serves sparse rows
   p->dense_ok = p->fp.bm != 0;
   int rc;
   if (p->fp.variant == 3 &&
@@ -1283,13 +1283,13 @@ int check_rows(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* X, int64_t
 }
 
 // What the three dense entry points do after their own argument checks: the
-// row image's checks, the d <= 1240 requirement, then the plan's lock (held
+// row image's checks, the d <= 1216 requirement, then the plan's lock (held
 // by the caller's lk until it returns) and the per-row queues.
 int dense_enter(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* X, int64_t n,
                 std::unique_lock<std::mutex>& lk) {
   if (int rc = check_rows(p, rows, X, n)) return rc;
   if (!p->dense_ok) {
-    cyc::set_error("d > 1240 is not supported by the LDS-resident assign kernel (dense rows)");
+    cyc::set_error("d > 1216 is not supported by the LDS-resident assign kernel (dense rows)");
     return CYC_ERR_UNSUPPORTED;
   }
   lk = std::unique_lock<std::mutex>(p->mu);

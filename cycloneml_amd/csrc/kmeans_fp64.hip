@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kAssignThreads, 1) void k_kmeans_assign(
 
   // Stage the BM x d block of X (zero padded to d4 and BM).
   {
-    const int total = rows * d;  // < 2^31: BM * d <= 64 * 1240
+    const int total = rows * d;  // < 2^31: BM * d <= 64 * 1216
     for (int e = tid; e < total; e += kAssignThreads) {
       int r = e / d, c = e - r * d;
       Xs[r * ldsStride + c] = X[CYC_GROW1(r) * d + c];
@@ -1065,6 +1065,9 @@ namespace {
 
 constexpr int kS3TB = 2;   // center tiles per wave group of k_kmeans_assign3
 
+// Widest d that fits: 16 rows need (16 s + 16 + kWaves * 16 * 4) * 8 <= 160 KiB,
+// s <= 1247; the strides == 2 (mod 32) below that are 1218 (d4 <= 1216) and
+// 1250 (d4 >= 1220), so d <= 1216.
 int pick_bm(int d4, int& stride, size_t& lds) {
   const int cands[3] = {64, 32, 16};
   const int maxbm = 64;

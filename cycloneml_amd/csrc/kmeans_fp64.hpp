@@ -16,7 +16,7 @@ namespace kmfp64 {
 // Everything the screens derive from (d, k) alone, filled by sizing().
 struct Sizing {
   int d = 0, k = 0, d4 = 0, kpad = 0;   // d4: d rounded up to 4, kpad: k to 16
-  // k_kmeans_assign: rows per workgroup (0: d > 1240, no LDS-resident dense
+  // k_kmeans_assign: rows per workgroup (0: d > 1216, no LDS-resident dense
   // assign), LDS row stride (== 2 mod 32 doubles) and bytes
   int bm = 0, ldsStride = 0;
   size_t assignLds = 0;

@@ -258,7 +258,7 @@ int cyc_kmeans_silhouette_score_dev(cyc_kmeans_plan plan, const double* X, const
  * assignments and costs are bit-identical; the cluster sums use the sparse
  * axpy (mllib BLAS.scala:93-112) with fp64 atomics (order-free to rounding).
  * xnorm = Vectors.norm of the stored values (cyc_row_norms_csr_dev).  The
- * plan's d is numFeatures; plans with d > 1240 serve only these calls. */
+ * plan's d is numFeatures; plans with d > 1216 serve only these calls. */
 int cyc_row_norms_csr_dev(const int64_t* rowptr, const double* vals, int64_t n, double* norms,
                           void* stream);
 /* statistics from the last cyc_kmeans_stats_dev on this plan */
