@@ -23,6 +23,7 @@ from .glm import (  # noqa: F401
     GeneralizedLinearRegressionModel,
     IterativelyReweightedLeastSquares,
 )
+from .recommendation import ALS, ALSModel, ALSPlan  # noqa: F401
 from .regression import (  # noqa: F401
     LinearRegression,
     LinearRegressionModel,

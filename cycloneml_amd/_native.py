@@ -190,6 +190,14 @@ SIGNATURES = {
     "cyc_gmm_accumulate_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "cyc_gmm_mstep_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "cyc_gmm_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "cyc_als_segment": (ctypes.c_int, []),
+    "cyc_als_side_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp,
+                                           ctypes.POINTER(_vp)]),
+    "cyc_als_side_destroy": (ctypes.c_int, [_vp]),
+    "cyc_als_yty_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "cyc_als_solve_dev": (ctypes.c_int, [_vp, _vp, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_als_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64,
+                                           _vp, _vp]),
     "cyc_csc_features": (_i32, [_vp]),
     "cyc_tiles_create": (ctypes.c_int, [_i32, _i64, _i64, ctypes.POINTER(_vp)]),
     "cyc_tiles_append_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),

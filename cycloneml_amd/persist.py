@@ -15,7 +15,10 @@ trained here loads in Spark (and back):
   - ml MultilayerPerceptronClassificationModel (ml/classification/
     MultilayerPerceptronClassifier.scala): `layers` in the metadata's paramMap
     and data/ = one parquet row Data(weights: ml Vector) (Spark 3); the reader
-    also takes the pre-3.0 row Data(layers: Array[Int], weights).
+    also takes the pre-3.0 row Data(layers: Array[Int], weights);
+  - ml ALSModel (ml/recommendation/ALS.scala, ALSModelWriter): metadata with
+    the extra field `rank`; userFactors/ and itemFactors/ = parquet rows (id:
+    Int, features: Array[Float]), one per id that had ratings in the fit.
 Vectors and matrices use the UDT struct encodings (ml/linalg/VectorUDT.scala,
 MatrixUDT.scala:30-70, mllib/linalg/Vectors.scala:271-280): type 1 = dense
 (values; matrices also numRows/numCols/isTransposed), type 0 = sparse.
@@ -379,6 +382,70 @@ def load_mlp_model(path):
             raise ValueError("the model's metadata holds no `layers` param")
         layers = [int(n) for n in params["layers"]]
     m = MultilayerPerceptronClassificationModel(layers, decode_vector(r["weights"]))
+    m.uid = meta.get("uid")
+    return m
+
+
+# -- ml ALSModel ---------------------------------------------------------------
+
+ALS_CLASS = "org.apache.spark.ml.recommendation.ALSModel"
+
+_ALS_DEFAULTS = {"userCol": "user", "itemCol": "item", "predictionCol": "prediction",
+                 "coldStartStrategy": "nan", "blockSize": 4096}
+
+
+def _host(a, dtype):
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def save_als_model(model, path, uid=None, overwrite=False):
+    """ALSModelWriter.saveImpl: `rank` as extra metadata, then the two factor
+    frames (id: Int, features: Array[Float]); ids without ratings in the fit
+    have no row."""
+    pa, _ = _pa()
+    _check_new_path(path, overwrite)
+    meta = {"class": ALS_CLASS, "timestamp": int(time.time() * 1000),
+            "sparkVersion": SPARK_VERSION, "uid": uid or f"als_{uuid.uuid4().hex[:12]}",
+            "paramMap": {"coldStartStrategy": model.coldStartStrategy},
+            "defaultParamMap": dict(_ALS_DEFAULTS), "rank": int(model.rank)}
+    _write_text(os.path.join(path, "metadata"), json.dumps(meta, separators=(",", ":")))
+    fields = [pa.field("id", pa.int32(), nullable=False),
+              pa.field("features", pa.list_(pa.field("element", pa.float32(), nullable=False)))]
+    spark = [_field("id", "integer", False),
+             _field("features", {"type": "array", "elementType": "float",
+                                 "containsNull": False})]
+    for name, F, present in (("userFactors", model.userFactors, model.userPresent),
+                             ("itemFactors", model.itemFactors, model.itemPresent)):
+        F = _host(F, np.float32)
+        ids = np.nonzero(_host(present, np.uint8))[0]
+        rows = [{"id": int(i), "features": [float(x) for x in F[i]]} for i in ids]
+        _write_parquet(os.path.join(path, name), fields, spark, rows)
+
+
+def load_als_model(path):
+    """ALSModelReader.load: rank from the metadata; the factor rows land at
+    their ids (the id range is 0 .. the largest saved id), other ids absent."""
+    from .recommendation import ALSModel
+    meta = json.loads(_read_text(os.path.join(path, "metadata")))
+    if meta.get("class") != ALS_CLASS:
+        raise ValueError(f"requirement failed: Error loading metadata: Expected class name "
+                         f"{ALS_CLASS} but found class name {meta.get('class')}")
+    rank = int(meta["rank"])
+    out = []
+    for name in ("userFactors", "itemFactors"):
+        rows = _read_parquet_rows(os.path.join(path, name))
+        n = 1 + max((int(r["id"]) for r in rows), default=-1)
+        F = np.zeros((n, rank), dtype=np.float32)
+        present = np.zeros(n, dtype=np.uint8)
+        for r in rows:
+            F[int(r["id"])] = np.asarray(r["features"], dtype=np.float32)
+            present[int(r["id"])] = 1
+        out += [F, present]
+    params = dict(meta.get("defaultParamMap", {}), **meta.get("paramMap", {}))
+    m = ALSModel(rank, out[0], out[2], out[1], out[3],
+                 params.get("coldStartStrategy", "nan"))
     m.uid = meta.get("uid")
     return m
 

@@ -772,6 +772,58 @@ int cyc_gmm_mstep_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, const d
 int cyc_gmm_predict_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, double* prob,
                         int32_t* label, double* logpdf, void* stream);
 
+/* ------------------------------------------------------------------ ALS */
+/* One half-step of ml/recommendation/ALS.scala's computeFactors
+ * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
+ * and the model's predict, 1 <= rank <= 64.
+ *
+ * A side (cyc_als_side_create) is the ratings grouped by destination id as a
+ * device CSR: rowptr (int64, m + 1), colidx (int32 source ids in [0, nsrc)),
+ * values (float32 ratings, nnz); duplicate pairs stay separate entries.  The
+ * three arrays are BORROWED: they stay alive and unchanged until
+ * cyc_als_side_destroy.  Creation checks the structure on the device
+ * (rowptr[0] == 0, rowptr non-decreasing, rowptr[m] == nnz, every colidx in
+ * range; a violation fails with "requirement failed: ..." before anything
+ * gathers through the arrays), counts each row's positive ratings and builds
+ * the table of segments (at most cyc_als_segment ratings of one row each)
+ * that every later solve walks.  It synchronizes the stream.
+ *
+ * cyc_als_solve_dev: Y (nsrc x rank float32, row-major) are the source
+ * factors.  Row u, each rating (i, r) in order, fp64: da = (double) Y[i],
+ * ata += c da da^T, atb += b da.  Explicit: c = 1, b = r, numExplicits = the
+ * row's rating count.  implicitPrefs: c1 = alpha |r|, c = c1, b = 1 + c1 where
+ * r > 0 and 0 elsewhere, numExplicits counts r > 0, and ata starts from YtY =
+ * sum_i da_i da_i^T over all nsrc source rows (yty: rank x rank fp64, full
+ * symmetric, from cyc_als_yty_dev; NULL: computed by the call).  Then ata's
+ * diagonal += regParam numExplicits, a Cholesky solve in fp64, X[u] (m x rank
+ * float32) = (float) solution.  present (m bytes) is 1 where the row has
+ * ratings; a row without ratings gets a zero factor and 0.  *info (device
+ * int64) is -1, or the lowest row whose factorization met a pivot that is not
+ * positive (that row's factor is zero; the other rows are solved as usual).
+ * The call does not synchronize: read info after the stream has run.
+ *
+ * cyc_als_predict_dev: out[p] = sdot(rank, U[users[p]], V[items[p]]) in fp32,
+ * the products added left to right, unfused; NaN where an id is negative, at
+ * or past its count, or marked absent (a NULL mask: every id present).
+ *
+ * fp64 MFMA, fixed-order sums, no floating-point atomics: two calls on the
+ * same inputs give the same bits. */
+typedef struct cyc_als_side_s* cyc_als_side;
+
+int cyc_als_segment(void);
+int cyc_als_side_create(const int64_t* rowptr, const int32_t* colidx, const float* values,
+                        int64_t m, int64_t nnz, int64_t nsrc, int32_t rank, void* stream,
+                        cyc_als_side* side);
+int cyc_als_side_destroy(cyc_als_side side);
+int cyc_als_yty_dev(cyc_als_side side, const float* Y, double* yty, void* stream);
+int cyc_als_solve_dev(cyc_als_side side, const float* Y, double regParam, int32_t implicitPrefs,
+                      double alpha, const double* yty, float* X, uint8_t* present, int64_t* info,
+                      void* stream);
+int cyc_als_predict_dev(const float* U, const uint8_t* userPresent, int64_t numUsers,
+                        const float* V, const uint8_t* itemPresent, int64_t numItems, int32_t rank,
+                        const int32_t* users, const int32_t* items, int64_t n, float* out,
+                        void* stream);
+
 /* ------------------------------------------------ summarizer pre-pass */
 /* The first pass of LogisticRegression.train (LogisticRegression.scala:
  * 511-516, Summarizer.getClassificationSummarizers, ml/stat/Summarizer.scala:
