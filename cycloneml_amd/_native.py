@@ -198,6 +198,15 @@ SIGNATURES = {
     "cyc_als_solve_dev": (ctypes.c_int, [_vp, _vp, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
     "cyc_als_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i64,
                                            _vp, _vp]),
+    "cyc_als_recommend_src_tile": (ctypes.c_int, []),
+    "cyc_als_recommend_dst_tile": (ctypes.c_int, [_i32]),
+    "cyc_als_recommend_max_num": (ctypes.c_int, []),
+    "cyc_als_recommend_lds_num": (ctypes.c_int, []),
+    "cyc_als_recommend_splits": (_i64, [_i64, _i64]),
+    "cyc_als_recommend_span": (_i64, [_i64, _i64]),
+    "cyc_als_recommend_workspace": (_i64, [_i64, _i64, _i32, _i32]),
+    "cyc_als_recommend_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32,
+                                             _i32, _vp, _vp, _vp, _i64, _vp]),
     "cyc_csc_features": (_i32, [_vp]),
     "cyc_tiles_create": (ctypes.c_int, [_i32, _i64, _i64, ctypes.POINTER(_vp)]),
     "cyc_tiles_append_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),

@@ -25,8 +25,27 @@ they are drawn by numpy.random.default_rng(seed) over the id range.  Spark's
 per-block XORShiftRandom draws and its in / out block partitioning are NOT
 restated, so a fit does not reproduce a Spark run's factors.
 
+Top-N (ALSModel.recommendForAll, csrc/als_recommend.hip).  The reference blocks
+both factor sets, scores a source row against a block of destinations by
+sgemv("T") through the Java BLAS (per destination an fp32 dot product, the
+products added left to right, unfused), keeps the num greatest per block and
+merges the blocks with TopByKeyAggregator.  Here one fused kernel scores and
+selects; the scores never reach memory.  score(u, j) has the same bits as
+predict gives for the pair.  Absent destinations are never candidates.  The
+order is score descending under java.lang.Float.compare (NaN canonical and above
+everything, -0.0 below +0.0); EQUAL SCORES GO TO THE LOWER DESTINATION ID.  Spark
+leaves ties to its bounded queue's internals; the rule is this project's, and
+it makes the order total, so blockSize (accepted, as in Spark) and the kernel's
+tiles and splits cannot change a result.  ALSModel.recommendForAllUsers /
+recommendForAllItems / recommendForUserSubset / recommendForItemSubset return
+(srcIds int32 [P], recIds int32 [P x n'], ratings float32 [P x n']) on the
+device: the P present source ids ascending (a subset: its distinct known and
+present ids; Spark's join drops the others too) and n' = min(num, present
+destinations), the length of Spark's arrays.
+
 Not provided: multi-rank fits (the factor all-gather between half-steps),
-recommendForAll*, nonnegative = True (NNLS), rank > 64.
+nonnegative = True (NNLS), rank > 64, more than MAX_RECOMMEND = 128
+recommendations per id.
 """
 from __future__ import annotations
 
@@ -40,6 +59,14 @@ from .regression import SingularMatrixException
 MAX_RANK = 64
 SEGMENT = 1024                # csrc/als.hip kSegment (cyc_als_segment)
 COLD_START = ("nan", "drop")
+MAX_RECOMMEND = 128           # csrc/als_recommend.hip kMaxNum (cyc_als_recommend_max_num)
+
+
+def check_num(num):
+    if int(num) < 1 or int(num) > MAX_RECOMMEND:
+        raise N.IllegalArgumentException(
+            "requirement failed: the number of recommendations must be in "
+            f"[1, {MAX_RECOMMEND}] but got {num}")
 
 
 def check_rank(rank):
@@ -153,6 +180,62 @@ class ALSPlan:
                                               N.ptr(items), n, N.ptr(out), N.stream_handle()))
         return out
 
+    # the shapes of csrc/als_recommend.hip (pure functions, no device needed)
+    def recommend_src_tile(self) -> int:
+        """Source rows per workgroup."""
+        return int(self._lib.cyc_als_recommend_src_tile())
+
+    def recommend_dst_tile(self) -> int:
+        """Destination rows per LDS tile at this rank."""
+        return int(self._lib.cyc_als_recommend_dst_tile(self.rank))
+
+    def recommend_max_num(self) -> int:
+        return int(self._lib.cyc_als_recommend_max_num())
+
+    def recommend_lds_num(self) -> int:
+        """The greatest num whose lists are kept in LDS (another path above)."""
+        return int(self._lib.cyc_als_recommend_lds_num())
+
+    def recommend_splits(self, m: int, ndst: int) -> int:
+        """Pieces the destination range is cut into for m requested rows."""
+        return int(self._lib.cyc_als_recommend_splits(int(m), int(ndst)))
+
+    def recommend_span(self, m: int, ndst: int) -> int:
+        """Destinations per piece: piece s is [s span, min(ndst, (s + 1) span))."""
+        return int(self._lib.cyc_als_recommend_span(int(m), int(ndst)))
+
+    def recommend_workspace(self, m: int, ndst: int, num: int) -> int:
+        return int(self._lib.cyc_als_recommend_workspace(int(m), int(ndst), self.rank, int(num)))
+
+    def recommend(self, S, srcPresent, D, dstPresent, num, srcIds=None):
+        """(ids int32 [m x num], scores float32 [m x num]) on the device: per
+        requested source row (srcIds, any order, repeats allowed; None: every
+        row of S) the num best present destinations, score descending under
+        Float.compare, ties to the lower id; -1 / NaN past the candidates and
+        in the whole row of a source id that is out of range or absent."""
+        import torch
+        check_num(num)
+        num = int(num)
+        ns, nd = int(S.shape[0]), int(D.shape[0])
+        self._factors(S, ns, "the source factors")
+        self._factors(D, nd, "the destination factors")
+        if srcPresent is not None:
+            _dev(srcPresent, torch.uint8, "the source mask", ns)
+        if dstPresent is not None:
+            _dev(dstPresent, torch.uint8, "the destination mask", nd)
+        m = ns
+        if srcIds is not None:
+            m = int(srcIds.numel()) if torch.is_tensor(srcIds) else -1
+            _dev(srcIds, torch.int32, "srcIds")
+        ids = torch.empty((m, num), dtype=torch.int32, device=S.device)
+        scores = torch.empty((m, num), dtype=torch.float32, device=S.device)
+        nbytes = self.recommend_workspace(m, nd, num)
+        ws = torch.empty(max(1, nbytes // 8), dtype=torch.int64, device=S.device)
+        N.check(self._lib.cyc_als_recommend_dev(
+            N.ptr(S), N.ptr(srcPresent), ns, N.ptr(srcIds), m, N.ptr(D), N.ptr(dstPresent), nd,
+            self.rank, num, N.ptr(ids), N.ptr(scores), N.ptr(ws), nbytes, N.stream_handle()))
+        return ids, scores
+
 
 def init_factors(present, rank: int, seed: int) -> np.ndarray:
     """len(present) x rank float32: a unit-norm row of standard normals per
@@ -230,6 +313,42 @@ class ALSModel:
         keep = torch.nonzero(~torch.isnan(p)).view(-1)
         return keep, p[keep]
 
+    def _recommend(self, forUsers, num, subset, blockSize):
+        import torch
+        check_num(num)
+        if int(blockSize) < 1:
+            raise N.IllegalArgumentException(f"ALS_blockSize given invalid value {blockSize}")
+        like = self.userFactors
+        if not (torch.is_tensor(like) and like.is_cuda):
+            like = torch.empty(0, device="cuda")
+        U, up, V, vp = self._device(like)
+        S, sp, D, dp = (U, up, V, vp) if forUsers else (V, vp, U, up)
+        src = subset_ids(torch.arange(S.shape[0], device=S.device) if subset is None else subset,
+                         sp)
+        keep = min(int(num), int(dp.sum()))
+        ids, scores = ALSPlan(self.rank).recommend(S, sp, D, dp, num, src)
+        return src, ids[:, :keep].contiguous(), scores[:, :keep].contiguous()
+
+    def recommendForAllUsers(self, numItems, blockSize=4096):
+        """(users int32 [P], items int32 [P x n'], ratings float32 [P x n']) on
+        the device: for each of the P present users, ascending, the n' =
+        min(numItems, present items) best items (score descending under
+        Float.compare, ties to the lower item id).  blockSize is accepted as in
+        Spark and has no effect on the result."""
+        return self._recommend(True, numItems, None, blockSize)
+
+    def recommendForAllItems(self, numUsers, blockSize=4096):
+        """The same with the sides swapped: per present item its best users."""
+        return self._recommend(False, numUsers, None, blockSize)
+
+    def recommendForUserSubset(self, users, numItems, blockSize=4096):
+        """recommendForAllUsers for the distinct ids of `users` that are known
+        and present, ascending (the others are dropped, as Spark's join does)."""
+        return self._recommend(True, numItems, users, blockSize)
+
+    def recommendForItemSubset(self, items, numUsers, blockSize=4096):
+        return self._recommend(False, numUsers, items, blockSize)
+
     def save(self, path, overwrite=False):
         from . import persist
         persist.save_als_model(self, path, overwrite=overwrite)
@@ -250,6 +369,20 @@ def _mask(present, factors):
     if torch.is_tensor(factors):
         return torch.ones(int(factors.shape[0]), dtype=torch.uint8, device=factors.device)
     return np.ones(int(factors.shape[0]), dtype=np.uint8)
+
+
+def subset_ids(ids, present):
+    """The distinct ids that are in [0, len(present)) and present, ascending
+    (int32, on present's device).  ids: a tensor, an array or a list of
+    integers; present: a uint8 / bool tensor or array."""
+    import torch
+    present = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
+    ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
+    if ids.numel() and (ids.dtype.is_floating_point or ids.dtype == torch.bool):
+        raise N.IllegalArgumentException("requirement failed: ids must be integers")
+    ids = torch.unique(ids.to(device=present.device, dtype=torch.int64).view(-1))
+    ids = ids[(ids >= 0) & (ids < present.numel())]
+    return ids[present[ids] != 0].to(torch.int32).contiguous()
 
 
 def check_cold_start(s):

@@ -806,6 +806,38 @@ int cyc_gmm_predict_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, doubl
  * the products added left to right, unfused; NaN where an id is negative, at
  * or past its count, or marked absent (a NULL mask: every id present).
  *
+ * cyc_als_recommend_dev: ALSModel.recommendForAll and the subset forms, a
+ * fused score + top-num pass.  S (nsrcRows x rank float32) are the source
+ * factors, D (ndst x rank float32) the destination factors; srcPresent /
+ * dstPresent are their presence masks (NULL: every id present).  srcIds (m
+ * int32) names the requested source rows, in any order and with repeats; NULL
+ * means rows 0 .. m - 1 (then m <= nsrcRows).  For requested row u and every
+ * PRESENT destination j, score(u, j) = ((0.0f + S[u,0] D[j,0]) + S[u,1] D[j,1])
+ * + ... in fp32, unfused: the same bits as cyc_als_predict_dev gives for the
+ * pair.  Candidates are ordered by score descending under
+ * java.lang.Float.compare (NaN is canonical, 0x7fc00000, and above everything;
+ * -0.0 is below +0.0); EQUAL SCORES GO TO THE LOWER DESTINATION ID.  Spark
+ * leaves ties to its bounded queue's internals; this total order is this
+ * library's own, so the answer does not depend on tiles, splits or merge order
+ * and two calls give the same bytes.  Row u of ids (m x num int32) and scores
+ * (m x num float32) holds the first num candidates in that order; with fewer
+ * than num present destinations the tail is -1 / NaN.  A source id that is
+ * negative, at or past nsrcRows, or absent gives a whole row of -1 / NaN, and
+ * nothing is gathered through it (the rule of cyc_als_predict_dev).
+ * workspace: at least cyc_als_recommend_workspace(m, ndst, rank, num) device
+ * bytes, 8-byte aligned, the call's alone until the stream has run it.  The
+ * call keeps no state and does not synchronize.  rank outside 1 .. 64, num < 1
+ * or above cyc_als_recommend_max_num() (128) and a short workspace fail with
+ * "requirement failed: ..." before any launch.
+ * The shape queries (pure functions of their arguments, the same on every
+ * device): cyc_als_recommend_src_tile() source rows per workgroup;
+ * cyc_als_recommend_dst_tile(rank) destination rows per LDS tile (0 for a bad
+ * rank); cyc_als_recommend_lds_num() the greatest num whose lists are kept
+ * in LDS (above it they live in the workspace: another path, the same
+ * result); cyc_als_recommend_splits(m, ndst) the number of pieces the
+ * destination range is cut into and cyc_als_recommend_span(m, ndst) their
+ * length (split s covers [s span, min(ndst, (s + 1) span))).
+ *
  * fp64 MFMA, fixed-order sums, no floating-point atomics: two calls on the
  * same inputs give the same bits. */
 typedef struct cyc_als_side_s* cyc_als_side;
@@ -823,6 +855,18 @@ int cyc_als_predict_dev(const float* U, const uint8_t* userPresent, int64_t numU
                         const float* V, const uint8_t* itemPresent, int64_t numItems, int32_t rank,
                         const int32_t* users, const int32_t* items, int64_t n, float* out,
                         void* stream);
+int cyc_als_recommend_src_tile(void);
+int cyc_als_recommend_dst_tile(int32_t rank);
+int cyc_als_recommend_max_num(void);
+int cyc_als_recommend_lds_num(void);
+int64_t cyc_als_recommend_splits(int64_t m, int64_t ndst);
+int64_t cyc_als_recommend_span(int64_t m, int64_t ndst);
+int64_t cyc_als_recommend_workspace(int64_t m, int64_t ndst, int32_t rank, int32_t num);
+int cyc_als_recommend_dev(const float* S, const uint8_t* srcPresent, int64_t nsrcRows,
+                          const int32_t* srcIds, int64_t m, const float* D,
+                          const uint8_t* dstPresent, int64_t ndst, int32_t rank, int32_t num,
+                          int32_t* ids, float* scores, void* workspace, int64_t workspaceBytes,
+                          void* stream);
 
 /* ------------------------------------------------ summarizer pre-pass */
 /* The first pass of LogisticRegression.train (LogisticRegression.scala:
