@@ -17,9 +17,9 @@
 // x_i, S_j = sum_i r_ij x_i x_i^T.  Calls ADD into it.
 //
 // Kernels
-//   k_gmm_pack    every A_j^T into the image the E step stages as the MFMA B
-//                 operand (k_rmm_pack's image, one per component), explicit
-//                 zeros past d.  Once per cyc_gmm_set_model_dev.
+//   pack          row_gemm.hpp: every A_j^T into the image the E step stages
+//                 as the MFMA B operand, one per component, explicit zeros
+//                 past d.  Once per cyc_gmm_set_model_dev.
 //   k_gmm_estep   a workgroup (8 waves x 32 rows) owns a 256-row tile and walks
 //                 the components.  For component j the X values become the A
 //                 operand of v_mfma_f64_16x16x4f64 as x - mu_j (one VALU
@@ -37,7 +37,7 @@
 //                 lane's own p_ij and stores r_ij (TRAIN) or p_ij / s_i and
 //                 the argmax (lowest index on ties); each wave adds its rows'
 //                 om_i log s_i in a fixed order into one slab entry.
-//   k_gmm_fold_ll sums[0] += the slab, in wave order.
+//   fold_add      row_gemm.hpp: sums[0] += the slab, in a fixed order.
 //   k_gmm_mstep   sum_i r_ij z_i z_i^T over the augmented row z = [x, 1], so
 //                 M_j is column d and W_j entry (d, d), as aSum and wSum ride
 //                 k_wls_tiles.  A workgroup owns one pair of 32-column panels
@@ -79,6 +79,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "row_gemm.hpp"
 
 struct cyc_gmm_plan_s {
   std::mutex mu;
@@ -92,11 +93,11 @@ struct cyc_gmm_plan_s {
 
 namespace {
 
+// the image's tiling (kChunk, kPanelTiles), the E step's workgroup (kWaves,
+// kTileRows), pack and fold_add
+using namespace cyc::rowgemm;
+
 constexpr double kEps = 2.220446049250313e-16;   // ml.impl.Utils.EPSILON = 2^-52
-constexpr int kChunk = 16;                  // contraction indices per LDS chunk
-constexpr int kPanelTiles = 4;              // 16-column tiles per panel
-constexpr int kWaves = 8;                   // E step: waves per workgroup, 32 rows each
-constexpr int kTileRows = 32 * kWaves;
 constexpr int kEGrid = 4096;                // E step grid cap (ll slab: kEGrid x kWaves)
 constexpr int kMaxFeatures = 1024;
 constexpr int64_t kWorkspaceBytes = (int64_t)1 << 30;
@@ -107,25 +108,6 @@ constexpr int MLD = MP + 16;                // LDS row stride: rows kk, kk + 1 o
 constexpr int MG = 16;                      // components per workgroup
 constexpr int MGC = 4;                      // components per wave
 constexpr int64_t kSlabBytes = (int64_t)256 << 20;
-
-typedef double gmm_double4 __attribute__((ext_vector_type(4), aligned(8)));
-
-// Bp[j imgLen + ((chunk KT + tile) 4 + kk) 64 + lane] = A_j[col, f], f = chunk
-// kChunk + 4 (lane >> 4) + kk, col = 16 tile + (lane & 15); zero past d.
-__global__ __launch_bounds__(256) void k_gmm_pack(const double* __restrict__ A, int d, int KT,
-                                                  int64_t imgLen, int64_t total,
-                                                  double* __restrict__ Bp) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * 256) {
-    const int64_t j = e / imgLen, i = e % imgLen;
-    const int lane = (int)(i & 63), kk = (int)((i >> 6) & 3);
-    const int64_t t = i >> 8;
-    const int tile = (int)(t % KT);
-    const int64_t f = (t / KT) * kChunk + 4 * (lane >> 4) + kk;
-    const int col = tile * 16 + (lane & 15);
-    Bp[e] = (f < d && col < d) ? A[(j * d + col) * d + f] : 0.0;
-  }
-}
 
 // TRAIN: P (nrows x k) = r_ij, llSlab[workgroup kWaves + wave] = the wave's
 // sum of om_i log s_i, a negative or NaN row weight sets *flag (the row then
@@ -167,11 +149,11 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_gmm_estep(
       if (ch < nfull) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          const gmm_double4 v = *reinterpret_cast<const gmm_double4*>(xp[t] + f0);
+          const double4_a8 v = *reinterpret_cast<const double4_a8*>(xp[t] + f0);
 #pragma unroll
           for (int e = 0; e < 4; ++e) x[t][e] = v[e];
         }
-        const gmm_double4 v = *reinterpret_cast<const gmm_double4*>(mp + f0);
+        const double4_a8 v = *reinterpret_cast<const double4_a8*>(mp + f0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) m[e] = v[e];
       } else {
@@ -362,23 +344,6 @@ __global__ __launch_bounds__(64 * kWaves, 2) void k_gmm_estep(
   }
 }
 
-// *ll += sum_w slab[w]: thread t sums w = t, t + 256, .. in order, then a
-// fixed LDS tree.
-__global__ __launch_bounds__(256) void k_gmm_fold_ll(const double* __restrict__ slab,
-                                                     int64_t waves, double* __restrict__ ll) {
-  __shared__ double sh[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int64_t w = t; w < waves; w += 256) s += slab[w];
-  sh[t] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) sh[t] += sh[t + h];
-    __syncthreads();
-  }
-  if (t == 0) *ll += sh[0];
-}
-
 // slab[((split k + j) pairs + pair) 1024 + a 32 + b] = sum over the split's
 // rows of R[row][j] z[I0 + a] z[J0 + b], z = [x, 1] (zero past d).  blockIdx.x
 // = pair of panels (upper block triangle), y = component group, z = split.
@@ -522,8 +487,6 @@ __global__ __launch_bounds__(256) void k_gmm_fold(const double* __restrict__ sla
   *dst += s;
 }
 
-inline int tiles16(int x) { return x / 16 + (x % 16 != 0); }
-
 const double* model_w(cyc_gmm_plan_s* p) { return (const double*)p->model.ptr; }
 const double* model_mu(cyc_gmm_plan_s* p) { return model_w(p) + p->k; }
 const double* model_u(cyc_gmm_plan_s* p) { return model_mu(p) + (int64_t)p->k * p->d; }
@@ -596,8 +559,7 @@ int cyc_gmm_plan_create(int32_t k, int32_t numFeatures, int64_t chunkRows, cyc_g
   auto* p = new cyc_gmm_plan_s();
   p->k = k;
   p->d = numFeatures;
-  const int T = tiles16(numFeatures);
-  p->imgLen = (int64_t)T * T * 256;
+  p->imgLen = packed_len(numFeatures, numFeatures);
   // chunkRows k doubles of r within the cap; whole row tiles when it allows
   if (chunkRows == 0) {
     chunkRows = std::max<int64_t>(1, kWorkspaceBytes / (8 * (int64_t)k));
@@ -628,11 +590,9 @@ int cyc_gmm_set_model_dev(cyc_gmm_plan plan, const double* weights, const double
   CYC_HIP(hipMemcpyAsync(m, weights, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
   CYC_HIP(hipMemcpyAsync(m + k, means, sizeof(double) * k * d, hipMemcpyDeviceToDevice, st));
   CYC_HIP(hipMemcpyAsync(m + k + k * d, u, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
-  const int64_t total = k * p->imgLen;
-  hipLaunchKernelGGL(k_gmm_pack, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)),
-                     dim3(256), 0, st, rootSigmaInv, (int)d, tiles16((int)d), p->imgLen, total,
-                     (double*)p->pack.ptr);
-  CYC_LAUNCH_CHECK("k_gmm_pack");
+  // B_j(f, col) = A_j[col, f]: A_j^T
+  if (int rc = pack(rootSigmaInv, (int)d, (int)d, 1, d, k, d * d, (double*)p->pack.ptr, st))
+    return rc;
   p->haveModel = true;
   return CYC_OK;
 }
@@ -660,9 +620,7 @@ int cyc_gmm_accumulate_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, co
     int64_t waves = 0;
     if (int rc = estep<true>(p, Xc, rows, w ? w + r0 : nullptr, R, nullptr, nullptr, &waves, st))
       return rc;
-    hipLaunchKernelGGL(k_gmm_fold_ll, dim3(1), dim3(256), 0, st, (const double*)p->llSlab.ptr,
-                       waves, sums);
-    CYC_LAUNCH_CHECK("k_gmm_fold_ll");
+    if (int rc = fold_add((const double*)p->llSlab.ptr, waves, sums, st)) return rc;
     if (int rc = mstep(p, Xc, rows, R, sums, st)) return rc;
   }
   int bad = 0;

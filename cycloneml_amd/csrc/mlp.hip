@@ -16,21 +16,17 @@
 // by s_i once.
 //
 // Kernels
-//   k_mlp_pack     a matrix given by two strides into the image k_mlp_gemm
-//                  stages (the one of rowmatrix_multiply.hip): W_l^T for the
-//                  forward pass, W_{l+1} for the delta pass.  Once per call.
-//   k_mlp_gemm<CT, EPI>
-//                  Y = epilogue(X B), the tiling of k_rmm_dense (8 waves x 32
-//                  rows, panels of CT <= 4 column tiles, X straight into the
-//                  MFMA A registers one chunk ahead, B through two LDS
-//                  buffers).  EPI_SIGMOID: 1 / (1 + exp(-(acc + b))),
-//                  EPI_BIAS: acc + b (z_L), EPI_DERIV: acc a (1 - a).
+//   gemm           row_gemm.hpp: pack() writes W_l^T (forward pass) and
+//                  W_{l+1} (delta pass) as images once per call, and
+//                  k_row_gemm<CT, Epi> computes Y = epilogue(X B) (timer
+//                  "k_mlp_gemm").  Sigmoid: 1 / (1 + exp(-(acc + b))), Bias:
+//                  acc + b (z_L), Deriv: acc a (1 - a).
 //   k_mlp_softmax<LPR, TRAIN>
 //                  LPR = 4 / 16 / 64 lanes per row over z_L: max, exp, sum.
 //                  TRAIN: -log p_y, delta_L = s_i (p - onehot(y)), the label
-//                  check, one loss partial per wave (k_mlp_fold_loss folds
-//                  them in a fixed order).  Otherwise raw / probability /
-//                  argmax (lowest index on ties).
+//                  check, one loss partial per wave (fold_add folds them in
+//                  a fixed order).  Otherwise raw / probability / argmax
+//                  (lowest index on ties).
 //   k_mlp_grad<MT, NT>
 //                  [gW_l | gb_l] = D_l^T [A_{l-1} | 1] on v_mfma_f64_16x16x4f64,
 //                  split-K over rows: one wave per (16 MT x 16 NT tile, row
@@ -50,6 +46,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "row_gemm.hpp"
 
 struct cyc_mlp_plan_s {
   std::mutex mu;
@@ -67,165 +64,35 @@ struct cyc_mlp_plan_s {
 
 namespace {
 
-constexpr int kChunk = 16;                  // contraction indices per LDS chunk
-constexpr int kPanelTiles = 4;              // 16-column tiles per pass over the rows
-constexpr int kWaves = 8;                   // waves per workgroup, 32 rows each
-constexpr int kTileRows = 32 * kWaves;
-constexpr int64_t kMaxGrid = 1 << 20;
+using namespace cyc::rowgemm;
+
 constexpr int kMaxWidth = 4096;
 constexpr int64_t kWorkspaceBytes = (int64_t)1 << 30;
 constexpr int kLossBlocks = 1024;           // k_mlp_softmax grid cap (4 waves each)
 
-enum { EPI_SIGMOID = 0, EPI_BIAS = 1, EPI_DERIV = 2 };
-
-// four doubles of a row: rows start at any multiple of 8 bytes
-typedef double mlp_double4 __attribute__((ext_vector_type(4), aligned(8)));
-
-// Bp[((chunk KT + tile) 4 + kk) 64 + lane] = B(f, col), f = chunk kChunk +
-// 4 (lane >> 4) + kk, col = 16 tile + (lane & 15); B(f, col) = B[f sf + col sc]
-// (n contraction indices, k columns, KT column tiles), zero past either.
-__global__ __launch_bounds__(256) void k_mlp_pack(const double* __restrict__ B, int n, int k,
-                                                  int64_t sf, int64_t sc, int KT, int64_t total,
-                                                  double* __restrict__ Bp) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(e & 63), kk = (int)((e >> 6) & 3);
-    const int64_t t = e >> 8;
-    const int tile = (int)(t % KT);
-    const int64_t f = (t / KT) * kChunk + 4 * (lane >> 4) + kk;
-    const int col = tile * 16 + (lane & 15);
-    Bp[e] = (f < n && col < k) ? B[f * sf + col * sc] : 0.0;
+// k_row_gemm's epilogues.  bias: the layer's k biases; act: the activations
+// (nrows x k).  The sigmoid keeps 4 waves per SIMD at CT = 1 only (its exp
+// spills at 128 registers beside two tiles' accumulators).
+struct Sigmoid {
+  static constexpr int kWideCT = 1;
+  const double* bias;
+  __device__ double operator()(double v, int64_t, int col, int) const {
+    return 1.0 / (1.0 + exp(-(v + bias[col])));
   }
-}
-
-// Column tiles [ct0 + panel CT, + CT) of Y = epilogue(X B) for every 256-row
-// tile; work item w = row tile x panels + panel.  aux: the bias (k) for
-// EPI_SIGMOID / EPI_BIAS, the activations (nrows x k) for EPI_DERIV.
-// Two workgroups per CU (4 waves per SIMD) up to CT = 2, but CT = 1 with the
-// sigmoid (its exp spills at 128 registers beside two tiles' accumulators).
-template <int CT, int EPI>
-__global__ __launch_bounds__(64 * kWaves, CT <= (EPI == EPI_SIGMOID ? 1 : 2) ? 4 : 2) void k_mlp_gemm(
-    const double* __restrict__ X, int64_t nrows, int n, int k, const double* __restrict__ Bp,
-    int KT, int ct0, int panels, const double* __restrict__ aux, double* __restrict__ Y) {
-  constexpr int CH = 256 * CT;                                  // doubles per staged chunk
-  constexpr int PT = (CH + 64 * kWaves - 1) / (64 * kWaves);    // per thread
-  __shared__ double Bs[2][CH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4;
-  const int nfull = n / kChunk, nch = nfull + (n % kChunk != 0);
-  const int64_t total = (nrows + kTileRows - 1) / kTileRows * panels;
-  for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {
-    const int ctb = ct0 + (int)(w % panels) * CT;
-    const int64_t r0 = w / panels * kTileRows + wave * 32;
-    // rows past nrows read the last row and indices past n the last index: a
-    // valid address and no branch around a load; the multiply replaces both
-    // by explicit zeros when it reads the registers
-    const double* xp[2];
-    bool ok[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int64_t row = r0 + t * 16 + (lane & 15);
-      ok[t] = row < nrows;
-      xp[t] = X + (ok[t] ? row : nrows - 1) * n;
-    }
-    auto loadX = [&](int ch, double (&x)[2][4]) {
-      const int64_t f0 = (int64_t)ch * kChunk + 4 * g;
-      if (ch < nfull) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const mlp_double4 v = *reinterpret_cast<const mlp_double4*>(xp[t] + f0);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) x[t][j] = v[j];
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) x[t][j] = xp[t][std::min<int64_t>(f0 + j, n - 1)];
-      }
-    };
-    auto loadB = [&](int ch, double (&b)[PT]) {
-      const double* src = Bp + ((int64_t)ch * KT + ctb) * 256;
-#pragma unroll
-      for (int q = 0; q < PT; ++q) b[q] = src[min(tid + q * 64 * kWaves, CH - 1)];
-    };
-    auto storeB = [&](int ch, const double (&b)[PT]) {
-#pragma unroll
-      for (int q = 0; q < PT; ++q) {
-        const int e = tid + q * 64 * kWaves;
-        if (e < CH) Bs[ch & 1][e] = b[q];
-      }
-    };
-    cyc_double4 acc[2][CT];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) acc[t][ct] = cyc_double4{0.0, 0.0, 0.0, 0.0};
-    double xa[2][4], xb[2][4], bn[PT];
-    __syncthreads();   // the previous item's last chunk is read
-    loadB(0, bn);
-    loadX(0, xa);
-    storeB(0, bn);
-    __syncthreads();
-    // chunk ch: issue chunk ch + 1's loads, multiply, park the next B chunk
-    // in the other buffer (free since the barrier that ended chunk ch - 1)
-    auto step = [&](int ch, double (&xc)[2][4], double (&xn)[2][4]) {
-      const bool more = ch + 1 < nch;
-      if (more) {
-        loadB(ch + 1, bn);
-        loadX(ch + 1, xn);
-      }
-      const double* W = Bs[ch & 1];
-      const int64_t f0 = (int64_t)ch * kChunk + 4 * g;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const bool in = f0 + kk < n;
-        const double a0 = (ok[0] && in) ? xc[0][kk] : 0.0;
-        const double a1 = (ok[1] && in) ? xc[1][kk] : 0.0;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-          const double b = W[(ct * 4 + kk) * 64 + lane];
-          acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
-          acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
-        }
-      }
-      if (more) {
-        storeB(ch + 1, bn);
-        __syncthreads();
-      }
-    };
-    for (int ch = 0; ch < nch; ch += 2) {
-      step(ch, xa, xb);
-      if (ch + 1 < nch) step(ch + 1, xb, xa);
-    }
-    // lane holds rows 16 t + g + 4 r, column (lane & 15) of each tile
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-      const int col = (ctb + ct) * 16 + (lane & 15);
-      if (col >= k) continue;
-      double bias = 0.0;
-      if constexpr (EPI != EPI_DERIV) bias = aux[col];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t row = r0 + t * 16 + g + 4 * r;
-          if (row >= nrows) continue;
-          const double v = acc[t][ct][r];
-          double out;
-          if constexpr (EPI == EPI_SIGMOID) {
-            out = 1.0 / (1.0 + exp(-(v + bias)));
-          } else if constexpr (EPI == EPI_BIAS) {
-            out = v + bias;
-          } else {
-            const double a = aux[row * k + col];
-            out = v * (a * (1.0 - a));
-          }
-          Y[row * k + col] = out;
-        }
-    }
+};
+struct Bias {
+  static constexpr int kWideCT = 2;
+  const double* bias;
+  __device__ double operator()(double v, int64_t, int col, int) const { return v + bias[col]; }
+};
+struct Deriv {
+  static constexpr int kWideCT = 2;
+  const double* act;
+  __device__ double operator()(double v, int64_t row, int col, int k) const {
+    const double a = act[row * k + col];
+    return v * (a * (1.0 - a));
   }
-}
+};
 
 // One row of z_L (C classes) per LPR lanes.  Rows [0, nrows) of a chunk that
 // starts at row row0 of a shard of shardRows rows.
@@ -305,23 +172,6 @@ __global__ __launch_bounds__(256) void k_mlp_softmax(
     for (int t = LPR; t < 64; t <<= 1) lossAcc += __shfl_xor(lossAcc, t);
     if (lane == 0) lossSlab[gw] = lossAcc;
   }
-}
-
-// *loss += sum_w slab[w]: thread t sums w = t, t + 256, .. in order, then a
-// fixed LDS tree.
-__global__ __launch_bounds__(256) void k_mlp_fold_loss(const double* __restrict__ slab,
-                                                       int64_t waves, double* __restrict__ loss) {
-  __shared__ double sh[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int64_t w = t; w < waves; w += 256) s += slab[w];
-  sh[t] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) sh[t] += sh[t + h];
-    __syncthreads();
-  }
-  if (t == 0) *loss += sh[0];
 }
 
 // slab[sp][o + j no] = sum over rows [sp rps, (sp + 1) rps) of D[r][o] Aj[r],
@@ -413,42 +263,6 @@ __global__ __launch_bounds__(256) void k_mlp_fold_grad(const double* __restrict_
   }
 }
 
-inline int tiles16(int x) { return x / 16 + (x % 16 != 0); }
-inline int64_t packed_len(int n, int k) {
-  return (int64_t)(n / kChunk + (n % kChunk != 0)) * tiles16(k) * 256;
-}
-
-int pack(const double* B, int n, int k, int64_t sf, int64_t sc, double* Bp, hipStream_t st) {
-  const int64_t total = packed_len(n, k);
-  hipLaunchKernelGGL(k_mlp_pack, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)),
-                     dim3(256), 0, st, B, n, k, sf, sc, tiles16(k), total, Bp);
-  CYC_LAUNCH_CHECK("k_mlp_pack");
-  return CYC_OK;
-}
-
-template <int CT, int EPI>
-void launch_gemm(const double* X, int64_t nrows, int n, int k, const double* Bp, int KT, int ct0,
-                 int panels, const double* aux, double* Y, hipStream_t st) {
-  const int64_t total = (nrows + kTileRows - 1) / kTileRows * panels;
-  hipLaunchKernelGGL((k_mlp_gemm<CT, EPI>), dim3((unsigned)std::min(total, kMaxGrid)),
-                     dim3(64 * kWaves), 0, st, X, nrows, n, k, Bp, KT, ct0, panels, aux, Y);
-}
-
-// Y (nrows x k) = epilogue(X (nrows x n) B), Bp the packed B
-template <int EPI>
-int gemm(const double* X, int64_t nrows, int n, int k, const double* Bp, const double* aux,
-         double* Y, hipStream_t st) {
-  cyc::KernelTimer timer("k_mlp_gemm", st);
-  const int KT = tiles16(k);
-  const int full = KT / kPanelTiles, rem = KT % kPanelTiles, c0 = full * kPanelTiles;
-  if (full) launch_gemm<kPanelTiles, EPI>(X, nrows, n, k, Bp, KT, 0, full, aux, Y, st);
-  if (rem == 1) launch_gemm<1, EPI>(X, nrows, n, k, Bp, KT, c0, 1, aux, Y, st);
-  if (rem == 2) launch_gemm<2, EPI>(X, nrows, n, k, Bp, KT, c0, 1, aux, Y, st);
-  if (rem == 3) launch_gemm<3, EPI>(X, nrows, n, k, Bp, KT, c0, 1, aux, Y, st);
-  CYC_LAUNCH_CHECK("k_mlp_gemm");
-  return CYC_OK;
-}
-
 template <bool TRAIN>
 int softmax(const double* Z, int64_t nrows, int C, const double* labels, int64_t row0,
             int64_t shardRows, int64_t blockSize, double totalBlocks, double* D, double* lossSlab,
@@ -531,7 +345,7 @@ int reserve_workspace(cyc_mlp_plan_s* p, int64_t chunk, bool deltas, Workspace* 
   return CYC_OK;
 }
 
-// W_l^T of every layer (and W_l, l >= 2, for the delta pass) in k_mlp_gemm's image
+// W_l^T of every layer (and W_l, l >= 2, for the delta pass) as k_row_gemm images
 int pack_weights(cyc_mlp_plan_s* p, const double* weights, bool backward, hipStream_t st) {
   if (int rc = p->packF.reserve(sizeof(double) * (size_t)p->pfLen)) return rc;
   if (backward)
@@ -540,10 +354,10 @@ int pack_weights(cyc_mlp_plan_s* p, const double* weights, bool backward, hipStr
     const int ni = p->layers[l - 1], no = p->layers[l];
     const double* W = weights + p->woff[l];
     // forward: B(i, o) = W[i no + o]
-    if (int rc = pack(W, ni, no, no, 1, (double*)p->packF.ptr + p->pfOff[l], st)) return rc;
+    if (int rc = pack(W, ni, no, no, 1, 1, 0, (double*)p->packF.ptr + p->pfOff[l], st)) return rc;
     // delta: D_{l-1} = D_l W_l, B(o, i) = W[i no + o]
     if (backward && l >= 2)
-      if (int rc = pack(W, no, ni, 1, no, (double*)p->packB.ptr + p->pbOff[l], st)) return rc;
+      if (int rc = pack(W, no, ni, 1, no, 1, 0, (double*)p->packB.ptr + p->pbOff[l], st)) return rc;
   }
   return CYC_OK;
 }
@@ -556,8 +370,8 @@ int forward_chunk(cyc_mlp_plan_s* p, const double* X, int64_t rows, const double
     const int ni = p->layers[l - 1], no = p->layers[l];
     const double* Bp = (const double*)p->packF.ptr + p->pfOff[l];
     const double* bias = weights + p->woff[l] + (int64_t)no * ni;
-    int rc = l < p->L ? gemm<EPI_SIGMOID>(in, rows, ni, no, Bp, bias, w.act[l], st)
-                      : gemm<EPI_BIAS>(in, rows, ni, no, Bp, bias, w.act[l], st);
+    int rc = l < p->L ? gemm(in, rows, ni, no, Bp, Sigmoid{bias}, w.act[l], "k_mlp_gemm", st)
+                      : gemm(in, rows, ni, no, Bp, Bias{bias}, w.act[l], "k_mlp_gemm", st);
     if (rc) return rc;
     in = w.act[l];
   }
@@ -653,15 +467,13 @@ int cyc_mlp_loss_grad_dev(cyc_mlp_plan plan, const double* X, const double* labe
                                (double)totalBlocks, w.delta[L], (double*)p->lossSlab.ptr,
                                (int*)p->flag.ptr, nullptr, nullptr, nullptr, &waves, st))
       return rc;
-    hipLaunchKernelGGL(k_mlp_fold_loss, dim3(1), dim3(256), 0, st,
-                       (const double*)p->lossSlab.ptr, waves, loss);
-    CYC_LAUNCH_CHECK("k_mlp_fold_loss");
+    if (int rc = fold_add((const double*)p->lossSlab.ptr, waves, loss, st)) return rc;
     for (int l = L; l >= 1; --l) {
       const int ni = p->layers[l - 1], no = p->layers[l];
       if (l >= 2) {   // D_{l-1} = (D_l W_l) a_{l-1} (1 - a_{l-1})
         const double* Bp = (const double*)p->packB.ptr + p->pbOff[l];
-        if (int rc = gemm<EPI_DERIV>(w.delta[l], rows, no, ni, Bp, w.act[l - 1], w.delta[l - 1],
-                                     st))
+        if (int rc = gemm(w.delta[l], rows, no, ni, Bp, Deriv{w.act[l - 1]}, w.delta[l - 1],
+                          "k_mlp_gemm", st))
           return rc;
       }
       if (int rc = layer_grad(p, w.delta[l], l >= 2 ? w.act[l - 1] : Xc, rows, no, ni,

@@ -5,26 +5,8 @@
 // .values), Y the nrows x k row-major product.
 //
 // Kernels
-//   k_rmm_pack     B into the image the dense kernel stages: for every chunk
-//                  of kChunk contraction indices and every 16-column tile, the
-//                  256 doubles in the order the MFMA B operand is read (k-step,
-//                  then lane), zero where the index or the column is past the
-//                  matrix.  n k elements, once per call.
-//   k_rmm_dense<CT>
-//                  v_mfma_f64_16x16x4f64, 8 waves x 32 rows per workgroup, a
-//                  panel of CT <= kPanelTiles column tiles (64 columns)
-//                  per pass over the rows.  X goes from HBM straight into
-//                  registers in the MFMA A layout -- lane (row l & 15, group
-//                  g = l >> 4) holds indices f0 + 4g .. 4g + 3 of its row for
-//                  k-steps 0..3 (the order within a chunk is permuted, the
-//                  same for every call: 128 contiguous bytes per row per
-//                  chunk) -- one chunk ahead of the multiply.  The chunk's
-//                  packed B panel is copied into one of two LDS buffers one
-//                  chunk ahead, one barrier per chunk; every B read is 64
-//                  consecutive doubles (no bank conflict, no padding).
-//                  k > 64: a launch over the full panels (consecutive
-//                  workgroups take the panels of one row tile, so the re-read
-//                  of X comes from L2) and one for the remaining CT tiles.
+//   dense          row_gemm.hpp: pack() writes B's image once per call and
+//                  k_row_gemm<CT, Store> multiplies (timer "k_rmm_dense").
 //   k_rmm_transpose
 //                  B^T (n x k row-major) for the CSR kernel's gathers.
 //   k_rmm_csr<LPR, NA>
@@ -49,150 +31,11 @@
 #include <utility>
 
 #include "common.hpp"
+#include "row_gemm.hpp"
 
 namespace {
 
-constexpr int kChunk = 16;                  // contraction indices per LDS chunk
-constexpr int kPanelTiles = 4;              // 16-column tiles per pass over the rows
-constexpr int kWaves = 8;                   // waves per workgroup, 32 rows each
-constexpr int kTileRows = 32 * kWaves;
-constexpr int64_t kMaxGrid = 1 << 20;
-
-// four doubles of a row: rows start at any multiple of 8 bytes
-typedef double rmm_double4 __attribute__((ext_vector_type(4), aligned(8)));
-
-// Bp[((chunk KT + tile) 4 + kk) 64 + lane] = B[chunk kChunk + 4 (lane >> 4) + kk]
-// [16 tile + (lane & 15)], KT = column tiles of B
-__global__ __launch_bounds__(256) void k_rmm_pack(const double* __restrict__ B, int n, int k,
-                                                  int KT, int64_t total,
-                                                  double* __restrict__ Bp) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(e & 63), kk = (int)((e >> 6) & 3);
-    const int64_t t = e >> 8;
-    const int tile = (int)(t % KT);
-    const int64_t f = (t / KT) * kChunk + 4 * (lane >> 4) + kk;
-    const int col = tile * 16 + (lane & 15);
-    Bp[e] = (f < n && col < k) ? B[f + (int64_t)col * n] : 0.0;
-  }
-}
-
-// Column tiles [ct0 + panel CT, + CT) of Y for every 256-row tile; work item
-// w = row tile x panels + panel.
-// Two workgroups per CU (4 waves per SIMD) up to CT = 2; the 16 CT accumulator
-// registers of a wider panel leave room for one (more would spill).
-template <int CT>
-__global__ __launch_bounds__(64 * kWaves, CT <= 2 ? 4 : 2) void k_rmm_dense(
-    const double* __restrict__ X, int64_t nrows, int n, int k, const double* __restrict__ Bp,
-    int KT, int ct0, int panels, double* __restrict__ Y) {
-  constexpr int CH = 256 * CT;                                  // doubles per staged chunk
-  constexpr int PT = (CH + 64 * kWaves - 1) / (64 * kWaves);    // per thread
-  __shared__ double Bs[2][CH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4;
-  const int nfull = n / kChunk, nch = nfull + (n % kChunk != 0);
-  const int64_t total = (nrows + kTileRows - 1) / kTileRows * panels;
-  for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {
-    const int ctb = ct0 + (int)(w % panels) * CT;
-    const int64_t r0 = w / panels * kTileRows + wave * 32;
-    // rows past nrows read the last row and indices past n the last index: a
-    // valid address and no branch around a load.  The multiply replaces both
-    // by explicit zeros when it reads the registers (not here: a select on a
-    // loaded value would wait for the load one chunk early).
-    const double* xp[2];
-    bool ok[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int64_t row = r0 + t * 16 + (lane & 15);
-      ok[t] = row < nrows;
-      xp[t] = X + (ok[t] ? row : nrows - 1) * n;
-    }
-    auto loadX = [&](int ch, double (&x)[2][4]) {
-      const int64_t f0 = (int64_t)ch * kChunk + 4 * g;   // n + 15 may pass 2^31
-      if (ch < nfull) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const rmm_double4 v = *reinterpret_cast<const rmm_double4*>(xp[t] + f0);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) x[t][j] = v[j];
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) x[t][j] = xp[t][std::min<int64_t>(f0 + j, n - 1)];
-      }
-    };
-    auto loadB = [&](int ch, double (&b)[PT]) {
-      const double* src = Bp + ((int64_t)ch * KT + ctb) * 256;
-#pragma unroll
-      for (int q = 0; q < PT; ++q) {
-        b[q] = src[min(tid + q * 64 * kWaves, CH - 1)];   // unconditional: no branch to wait at
-      }
-    };
-    auto storeB = [&](int ch, const double (&b)[PT]) {
-#pragma unroll
-      for (int q = 0; q < PT; ++q) {
-        const int e = tid + q * 64 * kWaves;
-        if (e < CH) Bs[ch & 1][e] = b[q];
-      }
-    };
-    cyc_double4 acc[2][CT];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) acc[t][ct] = cyc_double4{0.0, 0.0, 0.0, 0.0};
-    double xa[2][4], xb[2][4], bn[PT];
-    __syncthreads();   // the previous item's last chunk is read
-    loadB(0, bn);
-    loadX(0, xa);
-    storeB(0, bn);
-    __syncthreads();
-    // chunk ch: issue chunk ch + 1's loads, multiply, park the next B chunk
-    // in the other buffer (free since the barrier that ended chunk ch - 1)
-    auto step = [&](int ch, double (&xc)[2][4], double (&xn)[2][4]) {
-      const bool more = ch + 1 < nch;
-      if (more) {
-        loadB(ch + 1, bn);
-        loadX(ch + 1, xn);
-      }
-      const double* W = Bs[ch & 1];
-      const int64_t f0 = (int64_t)ch * kChunk + 4 * g;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const bool in = f0 + kk < n;
-        const double a0 = (ok[0] && in) ? xc[0][kk] : 0.0;
-        const double a1 = (ok[1] && in) ? xc[1][kk] : 0.0;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-          const double b = W[(ct * 4 + kk) * 64 + lane];
-          acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
-          acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
-        }
-      }
-      if (more) {
-        storeB(ch + 1, bn);
-        __syncthreads();
-      }
-    };
-    for (int ch = 0; ch < nch; ch += 2) {
-      step(ch, xa, xb);
-      if (ch + 1 < nch) step(ch + 1, xb, xa);
-    }
-    // lane holds rows 16 t + g + 4 r, column (lane & 15) of each tile
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = r0 + t * 16 + g + 4 * r;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-          const int col = (ctb + ct) * 16 + (lane & 15);
-          if (row < nrows && col < k) Y[row * k + col] = acc[t][ct][r];
-        }
-      }
-  }
-}
+using namespace cyc::rowgemm;
 
 // Bt[f k + l] = B[f + l n]
 __global__ __launch_bounds__(256) void k_rmm_transpose(const double* __restrict__ B, int n, int k,
@@ -283,14 +126,6 @@ int check_args(int64_t nrows, int32_t n, const double* B, int32_t k, const doubl
   return CYC_OK;
 }
 
-template <int CT>
-void launch_dense(const double* X, int64_t nrows, int n, int k, const double* Bp, int KT, int ct0,
-                  int panels, double* Y, hipStream_t st) {
-  const int64_t total = (nrows + kTileRows - 1) / kTileRows * panels;
-  hipLaunchKernelGGL((k_rmm_dense<CT>), dim3((unsigned)std::min(total, kMaxGrid)),
-                     dim3(64 * kWaves), 0, st, X, nrows, n, k, Bp, KT, ct0, panels, Y);
-}
-
 template <int LPR, int NA>
 void launch_csr(const int64_t* rowptr, const int32_t* colidx, const double* vals, int64_t nrows,
                 int k, const double* Bt, double* Y, hipStream_t st) {
@@ -309,23 +144,12 @@ int cyc_rowmatrix_multiply_dev(const double* X, int64_t nrows, int32_t n, const 
   if (nrows == 0) return CYC_OK;
   CYC_REQUIRE(X != nullptr, "non-null rows");
   hipStream_t st = cyc::as_stream(stream);
-  const int KT = k / 16 + (k % 16 != 0), nch = n / kChunk + (n % kChunk != 0);
-  const int64_t packed = (int64_t)nch * KT * 256;
   std::lock_guard<std::mutex> lock(g_mu);
   double* Bp = nullptr;
-  if (int rc = scratch_for(st, sizeof(double) * (size_t)packed, &Bp)) return rc;
-  hipLaunchKernelGGL(k_rmm_pack, dim3((unsigned)std::min<int64_t>((packed + 255) / 256, 4096)),
-                     dim3(256), 0, st, B, (int)n, (int)k, KT, packed, Bp);
-  CYC_LAUNCH_CHECK("k_rmm_pack");
-  cyc::KernelTimer timer("k_rmm_dense", st);
-  const int full = KT / kPanelTiles, rem = KT % kPanelTiles;
-  if (full)
-    launch_dense<kPanelTiles>(X, nrows, n, k, Bp, KT, 0, full, Y, st);
-  if (rem == 1) launch_dense<1>(X, nrows, n, k, Bp, KT, full * kPanelTiles, 1, Y, st);
-  if (rem == 2) launch_dense<2>(X, nrows, n, k, Bp, KT, full * kPanelTiles, 1, Y, st);
-  if (rem == 3) launch_dense<3>(X, nrows, n, k, Bp, KT, full * kPanelTiles, 1, Y, st);
-  CYC_LAUNCH_CHECK("k_rmm_dense");
-  return CYC_OK;
+  if (int rc = scratch_for(st, sizeof(double) * (size_t)packed_len(n, k), &Bp)) return rc;
+  // B(f, col) = B[f + col n]
+  if (int rc = pack(B, n, k, 1, n, 1, 0, Bp, st)) return rc;
+  return gemm(X, nrows, n, k, Bp, Store{}, Y, "k_rmm_dense", st);
 }
 
 int cyc_rowmatrix_multiply_csr_dev(const int64_t* rowptr, const int32_t* colidx,

@@ -32,8 +32,9 @@ from cycloneml_amd.classification import (
 
 pytestmark = pytest.mark.gpu
 
+# (5, 20) and (5, 40): the top layer's bias epilogue on 2 and 3 column tiles
 LAYERS = [(1, 1), (3, 2), (5, 1), (4, 5, 3), (17, 16, 15, 2), (16, 33, 4), (130, 65, 17, 3),
-          (64, 64, 64), (1025, 8, 129)]
+          (64, 64, 64), (1025, 8, 129), (5, 20), (5, 40)]
 # (rows, blockSize, chunkRows): the row counts at blockSize 128, the block
 # sizes at 257 rows, and 1000 rows in chunks of 256 (chunk edges inside
 # blocks, a 104-row tail block, a 232-row tail chunk)

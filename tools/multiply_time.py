@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Times RowMatrix.multiply (cyc_rowmatrix_multiply_dev, k_rmm_dense; CSR:
-cyc_rowmatrix_multiply_csr_dev, k_rmm_csr) beside torch.matmul (rocBLAS dgemm)
+"""Times RowMatrix.multiply (cyc_rowmatrix_multiply_dev, the shared k_row_gemm
+under the timer label k_rmm_dense; CSR: cyc_rowmatrix_multiply_csr_dev,
+k_rmm_csr) beside torch.matmul (rocBLAS dgemm)
 on the same device tensors, in one process: HIP events, the median of --runs
 runs after --warmup warm-ups.  One JSON line per shape (also appended to --out
 when given), with the share of
