@@ -10,6 +10,8 @@ from . import _native  # noqa: F401  (loads nothing until first use)
 from .classification import (  # noqa: F401
     MultilayerPerceptronClassificationModel,
     MultilayerPerceptronClassifier,
+    NaiveBayes,
+    NaiveBayesModel,
 )
 from .feature import PCA, PCAModel  # noqa: F401
 from .gmm import (  # noqa: F401

@@ -652,3 +652,108 @@ class MultilayerPerceptronClassifier:
             plan.close()
         summary = MultilayerPerceptronClassificationTrainingSummary(history)
         return MultilayerPerceptronClassificationModel(self.layers, state.x, summary)
+
+
+class NaiveBayesModel:
+    """ml.classification.NaiveBayesModel: pi (C), theta (C x d), sigma (C x d
+    for gaussian, else 0 x 0) on the host, with Spark's persistence layout.
+    Constructible from host arrays without a device.  Device predictions
+    (predict / predictRaw / predictProbability) are not provided yet."""
+
+    def __init__(self, pi, theta, sigma=None, modelType: str = "multinomial",
+                 smoothing: float = 1.0):
+        from . import naive_bayes as nb
+        nb.check_model_type(modelType)
+        self.modelType = modelType
+        self.smoothing = float(smoothing)
+        self.pi = np.array(pi, dtype=np.float64).ravel()
+        self.theta = np.array(theta, dtype=np.float64)
+        if self.theta.ndim != 2 or self.theta.shape[0] != self.pi.size or self.pi.size < 1 \
+                or self.theta.shape[1] < 1:
+            raise N.IllegalArgumentException(
+                "requirement failed: theta is numClasses x numFeatures and pi has numClasses "
+                "values")
+        nb.check_shape(self.pi.size, self.theta.shape[1])
+        if modelType == "gaussian":
+            if sigma is None or np.asarray(sigma).shape != self.theta.shape:
+                raise N.IllegalArgumentException(
+                    "requirement failed: a gaussian model needs sigma of theta's shape")
+            self.sigma = np.array(sigma, dtype=np.float64)
+        else:
+            if sigma is not None and np.asarray(sigma).size != 0:
+                raise N.IllegalArgumentException(
+                    f"requirement failed: a {modelType} model has no sigma")
+            self.sigma = np.zeros((0, 0), dtype=np.float64)
+
+    @property
+    def numClasses(self) -> int:
+        return self.pi.size
+
+    @property
+    def numFeatures(self) -> int:
+        return self.theta.shape[1]
+
+    def save(self, path, overwrite=False):
+        from . import persist
+        persist.save_naive_bayes_model(self, path, overwrite=overwrite)
+
+    @staticmethod
+    def load(path) -> "NaiveBayesModel":
+        from . import persist
+        return persist.load_naive_bayes_model(path)
+
+
+class NaiveBayes:
+    """NaiveBayes.trainWithLabelCheck: one device pass into the per-class sums
+    buffer, one all-reduce, the closed-form model on the host
+    (naive_bayes.m_step).  `thresholds` is not offered."""
+
+    def __init__(self, smoothing: float = 1.0, modelType: str = "multinomial",
+                 workspaceBytes: int = 0):
+        from . import naive_bayes as nb
+        if not smoothing >= 0:
+            raise N.IllegalArgumentException(f"smoothing given invalid value {smoothing}.")
+        nb.check_model_type(modelType)
+        self.smoothing = float(smoothing)
+        self.modelType = modelType
+        self.workspaceBytes = int(workspaceBytes)
+
+    def fit(self, X, y, weights=None, numClasses=None) -> NaiveBayesModel:
+        """X: this rank's dense fp64 device rows (n x d); y: its labels
+        (device, class indices); weights: its row weights (optional).
+        With several ranks every rank calls fit."""
+        import torch
+        from . import naive_bayes as nb, parallel
+        from .linalg import CSRRows
+        if isinstance(X, CSRRows):
+            raise N.IllegalArgumentException(
+                "NaiveBayes fits dense rows; the CSR aggregate is not provided")
+        if not torch.is_tensor(X) or X.dim() != 2:
+            raise N.IllegalArgumentException(
+                "requirement failed: rows must be an fp64 device tensor (n x numFeatures)")
+        X = X.to(torch.float64).contiguous()
+        d = int(X.shape[1])
+        y = torch.as_tensor(y, device=X.device).to(torch.float64).contiguous()
+        if weights is not None:
+            weights = torch.as_tensor(weights, device=X.device).to(torch.float64).contiguous()
+        if numClasses is None:
+            top = float(y.max().item()) if y.numel() else -1.0
+            top = parallel.max_over_ranks(top, X.device)
+            if not top >= 0 or top != math.floor(top):
+                raise N.IllegalArgumentException(
+                    "requirement failed: Classification labels should be integers in [0 to "
+                    f"numClasses - 1]. Found {top}.")
+            numClasses = int(top) + 1
+        nb.check_shape(numClasses, d)
+        C = int(numClasses)
+        plan = nb.NBPlan(C, d, self.modelType, self.workspaceBytes)
+        try:
+            sums = torch.zeros(plan.sumsLength, dtype=torch.float64, device=X.device)
+            parallel.agree(lambda: plan.accumulate(X, y, weights, sums))
+            parallel.allreduce_(sums)          # the treeAggregate merge
+            host = sums.cpu().numpy()
+        finally:
+            plan.close()
+        pi, theta, sigma = nb.m_step(host, C, d, self.modelType, self.smoothing)
+        return NaiveBayesModel(pi, theta, sigma if self.modelType == "gaussian" else None,
+                               self.modelType, self.smoothing)

@@ -453,3 +453,62 @@ def load_als_model(path):
 def read_metadata(path):
     """DefaultParamsReader.loadMetadata (ReadWrite.scala:585-615) -> dict."""
     return json.loads(_read_text(os.path.join(path, "metadata")))
+
+
+# -- ml NaiveBayesModel ----------------------------------------------------------
+
+NB_CLASS = "org.apache.spark.ml.classification.NaiveBayesModel"
+
+_NB_DEFAULTS = {"featuresCol": "features", "labelCol": "label", "predictionCol": "prediction",
+                "rawPredictionCol": "rawPrediction", "probabilityCol": "probability",
+                "smoothing": 1.0, "modelType": "multinomial"}
+
+
+def save_naive_bayes_model(model, path, uid=None, overwrite=False):
+    """NaiveBayesModelWriter.saveImpl (Spark 3): modelType and smoothing in
+    the metadata's paramMap; data/ = one parquet row Data(pi: Vector, theta:
+    Matrix, sigma: Matrix), sigma the empty 0 x 0 matrix except for gaussian."""
+    pa, _ = _pa()
+    _check_new_path(path, overwrite)
+    meta = {"class": NB_CLASS, "timestamp": int(time.time() * 1000),
+            "sparkVersion": SPARK_VERSION,
+            "uid": uid or f"nb_{uuid.uuid4().hex[:12]}",
+            "paramMap": {"modelType": model.modelType, "smoothing": float(model.smoothing)},
+            "defaultParamMap": dict(_NB_DEFAULTS)}
+    _write_text(os.path.join(path, "metadata"), json.dumps(meta, separators=(",", ":")))
+    fields = [pa.field("pi", _arrow_vector()), pa.field("theta", _arrow_matrix()),
+              pa.field("sigma", _arrow_matrix())]
+    spark = [_field("pi", _udt("vector")), _field("theta", _udt("matrix")),
+             _field("sigma", _udt("matrix"))]
+    row = {"pi": encode_dense_vector(model.pi), "theta": encode_dense_matrix(model.theta, True),
+           "sigma": encode_dense_matrix(np.asarray(model.sigma, dtype=np.float64).reshape(
+               model.theta.shape if model.modelType == "gaussian" else (0, 0)), True)}
+    _write_parquet(os.path.join(path, "data"), fields, spark, [row])
+
+
+def load_naive_bayes_model(path):
+    """NaiveBayesModelReader.load: Spark >= 3.0 reads Data(pi, theta, sigma);
+    earlier releases wrote Data(pi, theta), which loads as a model without
+    sigma (never gaussian)."""
+    from .classification import NaiveBayesModel
+    meta = json.loads(_read_text(os.path.join(path, "metadata")))
+    if meta.get("class") != NB_CLASS:
+        raise ValueError(f"requirement failed: Error loading metadata: Expected class name "
+                         f"{NB_CLASS} but found class name {meta.get('class')}")
+    params = dict(meta.get("defaultParamMap", {}), **meta.get("paramMap", {}))
+    rows = _read_parquet_rows(os.path.join(path, "data"))
+    if len(rows) != 1:
+        raise ValueError("expected one data row")
+    r = rows[0]
+    modelType = params.get("modelType", "multinomial")
+    sigma = None
+    if r.get("sigma") is not None:
+        sigma = decode_matrix(r["sigma"])
+        if sigma.size == 0:
+            sigma = None
+    elif modelType == "gaussian":
+        raise ValueError("a gaussian model's data holds no sigma")
+    m = NaiveBayesModel(decode_vector(r["pi"]), decode_matrix(r["theta"]), sigma, modelType,
+                        float(params.get("smoothing", 1.0)))
+    m.uid = meta.get("uid")
+    return m

@@ -772,6 +772,47 @@ int cyc_gmm_mstep_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, const d
 int cyc_gmm_predict_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, double* prob,
                         int32_t* label, double* logpdf, void* stream);
 
+/* ----------------------------------------------------------- NaiveBayes
+ * ml/classification/NaiveBayes.scala over row-major fp64 rows (nrows x
+ * numFeatures), 1 <= numClasses <= 1024, numFeatures <= 16,776,959.  modelType: 0
+ * multinomial, 1 complement, 2 bernoulli, 3 gaussian.
+ *
+ * Aggregate.  sums is numClasses (1 + numFeatures) doubles (gaussian:
+ * numClasses (1 + 2 numFeatures)), [W | S | Q]: W_c = sum of w_i, S_c[j] =
+ * sum of w_i x_ij, Q_c[j] = sum of w_i (x_ij x_ij) over the rows of label c
+ * (y, nrows doubles; w, nrows doubles or NULL for 1).  The calls ADD the
+ * rows' share; buffers of several calls (or ranks) merge by addition.  The
+ * same pass checks the rows: label integer-valued in [0, numClasses) (rule
+ * 1), weight >= 0 and not NaN (rule 2), values >= 0 (multinomial, complement)
+ * or 0 / 1 (bernoulli) (rule 3).  The lowest offending row and its rule go to
+ * *badRow / *badRule (-1 / 0 when none; either may be NULL) and the call
+ * fails with the reference's message (sums is then undefined).  A bad label
+ * is never used as an index.  The call synchronizes the stream to read the
+ * flag.  Dense rows only: there is no CSR aggregate.
+ *
+ * The model comes from the merged sums in closed form on the host
+ * (cycloneml_amd/naive_bayes.py m_step).  Scoring on the device is not part
+ * of this interface yet.
+ *
+ * workspaceBytes (0: 256 MiB) bounds the device workspace: the aggregate's
+ * run partials (more launches when it is smaller, never other sums).  It
+ * grows to one run when smaller than that.  cyc_nb_col_tile (columns of the
+ * numFeatures + 1 per lane group of the aggregate), cyc_nb_rows_per_run and
+ * cyc_nb_classes_per_pass report the plan's tiling.
+ * fp64 throughout, fixed-order reductions, no atomics on doubles: two calls
+ * on the same inputs give the same bits. */
+typedef struct cyc_nb_plan_s* cyc_nb_plan;
+
+int cyc_nb_plan_create(int32_t numClasses, int32_t numFeatures, int32_t modelType,
+                       int64_t workspaceBytes, cyc_nb_plan* plan);
+int cyc_nb_plan_destroy(cyc_nb_plan plan);
+int64_t cyc_nb_col_tile(cyc_nb_plan plan);
+int64_t cyc_nb_rows_per_run(cyc_nb_plan plan);
+int64_t cyc_nb_classes_per_pass(cyc_nb_plan plan);
+int cyc_nb_aggregate_dev(cyc_nb_plan plan, const double* X, int64_t nrows, const double* y,
+                         const double* w, double* sums, int64_t* badRow, int32_t* badRule,
+                         void* stream);
+
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
  * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
