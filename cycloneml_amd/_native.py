@@ -196,6 +196,12 @@ SIGNATURES = {
     "cyc_nb_rows_per_run": (_i64, [_vp]),
     "cyc_nb_classes_per_pass": (_i64, [_vp]),
     "cyc_nb_aggregate_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _pi64, _pi32, _vp]),
+    "cyc_nbmodel_create": (ctypes.c_int, [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp,
+                                          ctypes.POINTER(_vp)]),
+    "cyc_nbmodel_destroy": (ctypes.c_int, [_vp]),
+    "cyc_nbmodel_path": (_i32, [_vp]),
+    "cyc_nbmodel_chunk_rows": (_i64, [_vp]),
+    "cyc_nbmodel_score_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _pi64, _vp]),
     "cyc_als_segment": (ctypes.c_int, []),
     "cyc_als_side_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp,
                                            ctypes.POINTER(_vp)]),

@@ -657,8 +657,12 @@ class MultilayerPerceptronClassifier:
 class NaiveBayesModel:
     """ml.classification.NaiveBayesModel: pi (C), theta (C x d), sigma (C x d
     for gaussian, else 0 x 0) on the host, with Spark's persistence layout.
-    Constructible from host arrays without a device.  Device predictions
-    (predict / predictRaw / predictProbability) are not provided yet."""
+    Constructible from host arrays without a device.  predictRaw,
+    predictProbability and predict score contiguous fp64 device rows (n x
+    numFeatures) with csrc/naive_bayes_score.hip (naive_bayes.NBScorer, built
+    on first use and kept per device) and leave the results on the device.
+    In the linear forms a zero feature is skipped, so a -inf of theta
+    (smoothing = 0) under a zero adds nothing.  CSR rows are refused."""
 
     def __init__(self, pi, theta, sigma=None, modelType: str = "multinomial",
                  smoothing: float = 1.0):
@@ -684,6 +688,7 @@ class NaiveBayesModel:
                 raise N.IllegalArgumentException(
                     f"requirement failed: a {modelType} model has no sigma")
             self.sigma = np.zeros((0, 0), dtype=np.float64)
+        self._scorers = {}
 
     @property
     def numClasses(self) -> int:
@@ -692,6 +697,33 @@ class NaiveBayesModel:
     @property
     def numFeatures(self) -> int:
         return self.theta.shape[1]
+
+    def _score(self, X, **which):
+        from . import naive_bayes as nb
+        nb.check_rows(X, self.numFeatures)
+        if not X.is_cuda:
+            raise N.IllegalArgumentException(
+                "requirement failed: rows must be a contiguous fp64 device tensor (n x "
+                f"{self.numFeatures})")
+        s = self._scorers.get(X.device)
+        if s is None:
+            s = self._scorers[X.device] = nb.NBScorer(self.pi, self.theta, self.sigma,
+                                                      self.modelType, X.device)
+        return s.score(X, **which)
+
+    def predictRaw(self, X):
+        """The raw prediction of every row (n x numClasses, device): the class
+        log-likelihoods up to a constant; complement's are normalized."""
+        return self._score(X, raw=True)[0]
+
+    def predictProbability(self, X):
+        """exp(raw - max) / sum of it, of every row (n x numClasses, device)."""
+        return self._score(X, prob=True)[1]
+
+    def predict(self, X):
+        """The first index of the largest raw value as fp64 (DenseVector
+        .argmax), device."""
+        return self._score(X, pred=True)[2]
 
     def save(self, path, overwrite=False):
         from . import persist

@@ -22,7 +22,22 @@ here is within an ulp of it.
 This project's own rules: every class 0 .. C - 1 needs W_c > 0 (Spark's groupBy
 would silently renumber the classes); C is 1 to 1024; the fit takes dense rows
 only (there is no CSR aggregate); the model holds pi, theta and sigma on the
-host and has no device predictions yet; `thresholds` is not offered.
+host; `thresholds` is not offered.
+
+Scoring (csrc/naive_bayes_score.hip, cyc_nbmodel_* in include/cyclone.h).
+score_operands turns the model into b (C), M (C x d) and, gaussian, V and ls on
+the host; NBScorer holds their device image and scores dense fp64 device rows:
+  multinomial  raw_c = pi_c + sum_j x_j theta_cj
+  complement   t_c = sum_j x_j theta_cj, raw_c = t_c - (max t + log sum_c
+               exp(t_c - max))
+  bernoulli    raw_c = (pi_c + sum_j L_cj) + sum_j x_j (theta_cj - L_cj),
+               L = log1p(-exp theta)
+  gaussian     raw_c = pi_c - (sum_j (x_j - theta_cj)^2 / sigma_cj + sum_j log
+               sigma_cj) / 2
+probability = exp(raw - max) / sum_c exp(raw_c - max); predict = the first
+index of the largest raw.  In the linear forms a term with x_j == 0 is skipped
+(the reference's sparse dot), so 0 times a -inf of theta (smoothing = 0) adds
+nothing; Spark's dense gemv gives NaN there.  CSR rows are not scored.
 """
 from __future__ import annotations
 
@@ -35,6 +50,7 @@ from . import _native as N
 MODEL_TYPES = ("multinomial", "complement", "bernoulli", "gaussian")
 MAX_NUM_CLASSES = 1024
 RULE_LABEL, RULE_WEIGHT, RULE_VALUE = 1, 2, 3     # cyc_nb_aggregate_dev's badRule
+SCORERS = ("auto", "product", "plain")            # cyc_nbmodel_create's scorer
 
 
 def check_model_type(modelType: str) -> int:
@@ -189,3 +205,122 @@ class NBPlan:
                 ctypes.byref(row), ctypes.byref(rule), N.stream_handle()))
         finally:
             self.badRow, self.badRule = int(row.value), int(rule.value)
+
+
+def score_operands(pi, theta, sigma, modelType: str = "multinomial"):
+    """(b (C), M (C x d), V (C x d or None), ls (C or None), finite) in numpy
+    fp64, sums over j left to right: the operands of csrc/naive_bayes_score.hip.
+    b is pi (zeros for complement, pi + sum_j L_cj for bernoulli, L =
+    log1p(-exp theta)), M is theta (theta - L for bernoulli); gaussian adds V =
+    sigma and ls_c = sum_j log sigma_cj.  finite: no inf or NaN in M."""
+    check_model_type(modelType)
+    pi = np.ascontiguousarray(pi, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    C = pi.size
+    V = ls = None
+    with np.errstate(all="ignore"):
+        if modelType == "gaussian":
+            V = np.ascontiguousarray(sigma, dtype=np.float64)
+            ls = np.zeros(C)
+            for j in range(V.shape[1]):
+                ls = ls + np.log(V[:, j])
+            b, M = pi, theta
+        elif modelType == "bernoulli":
+            L = np.log1p(-np.exp(theta))
+            b = pi + _rowsum(L)
+            M = theta - L
+        elif modelType == "complement":
+            b, M = np.zeros(C), theta
+        else:
+            b, M = pi, theta
+    return b, M, V, ls, bool(np.isfinite(M).all())
+
+
+def check_rows(X, numFeatures: int, what: str = "model") -> int:
+    """The row count of dense fp64 rows of this width; CSR rows are refused."""
+    import torch
+    from .linalg import CSRRows
+    if isinstance(X, CSRRows):
+        raise N.IllegalArgumentException(
+            "NaiveBayesModel scores dense rows; the CSR form is not provided")
+    if not torch.is_tensor(X) or X.dtype != torch.float64 or X.dim() != 2 \
+            or not X.is_contiguous():
+        raise N.IllegalArgumentException(
+            "requirement failed: rows must be a contiguous fp64 device tensor (n x "
+            f"{numFeatures})")
+    if int(X.shape[1]) != numFeatures:
+        raise N.IllegalArgumentException(
+            f"requirement failed: the rows have {int(X.shape[1])} features but the {what} has "
+            f"{numFeatures}")
+    return int(X.shape[0])
+
+
+class NBScorer:
+    """cyc_nbmodel: the device image of one model's scoring operands
+    (score_operands) and the workspace (workspaceBytes 0: 256 MiB).  scorer:
+    "auto" (the MFMA product for a linear form with a finite M, else the plain
+    kernel), "product" or "plain".  path is the one chosen."""
+
+    def __init__(self, pi, theta, sigma=None, modelType: str = "multinomial", device=None,
+                 workspaceBytes: int = 0, scorer: str = "auto"):
+        import torch
+        self.typeCode = check_model_type(modelType)
+        if scorer not in SCORERS:
+            raise N.IllegalArgumentException(
+                f"scorer given invalid value {scorer}. Supported options: " + ", ".join(SCORERS)
+                + ".")
+        b, M, V, ls, self.finite = score_operands(pi, theta, sigma, modelType)
+        check_shape(b.size, M.shape[1])
+        self.numClasses, self.numFeatures = int(b.size), int(M.shape[1])
+        self.modelType = modelType
+        if scorer == "product" and (modelType == "gaussian" or not self.finite):
+            raise N.IllegalArgumentException(
+                "requirement failed: the product scorer serves the linear forms with a finite "
+                "model matrix; this model takes the plain scorer")
+        self._lib = N.load()
+        self.device = torch.device("cuda:0" if device is None else device)
+        with torch.cuda.device(self.device):
+            dv = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+                  for a in (b, M, V, ls)]
+            h = ctypes.c_void_p()
+            N.check(self._lib.cyc_nbmodel_create(
+                self.numClasses, self.numFeatures, self.typeCode, int(workspaceBytes),
+                N.ptr(dv[0]), N.ptr(dv[1]), N.ptr(dv[2]), N.ptr(dv[3]), SCORERS.index(scorer),
+                N.stream_handle(), ctypes.byref(h)))
+        self.handle = h
+        self.badRow = -1
+        self.path = SCORERS[int(self._lib.cyc_nbmodel_path(h))]
+        self.chunkRows = int(self._lib.cyc_nbmodel_chunk_rows(h))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.cyc_nbmodel_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def score(self, X, raw=False, prob=False, pred=False):
+        """(raw (n x C), prob (n x C), pred (n, fp64)) device tensors, None
+        where not asked for.  badRow keeps the lowest offending row when the
+        call raises."""
+        import torch
+        n = check_rows(X, self.numFeatures, "scorer")
+        if not (raw or prob or pred):
+            raise N.IllegalArgumentException(
+                "requirement failed: one of raw, prob and pred must be asked for")
+        C = self.numClasses
+        out = [torch.empty((n, C), dtype=torch.float64, device=X.device) if raw else None,
+               torch.empty((n, C), dtype=torch.float64, device=X.device) if prob else None,
+               torch.empty(n, dtype=torch.float64, device=X.device) if pred else None]
+        self.badRow = -1
+        if n == 0:
+            return tuple(out)
+        row = ctypes.c_int64(-1)
+        try:
+            with torch.cuda.device(X.device):
+                N.check(self._lib.cyc_nbmodel_score_dev(
+                    self.handle, N.ptr(X), n, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]),
+                    ctypes.byref(row), N.stream_handle()))
+        finally:
+            self.badRow = int(row.value)
+        return tuple(out)

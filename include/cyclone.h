@@ -791,8 +791,8 @@ int cyc_gmm_predict_dev(cyc_gmm_plan plan, const double* X, int64_t nrows, doubl
  * flag.  Dense rows only: there is no CSR aggregate.
  *
  * The model comes from the merged sums in closed form on the host
- * (cycloneml_amd/naive_bayes.py m_step).  Scoring on the device is not part
- * of this interface yet.
+ * (cycloneml_amd/naive_bayes.py m_step).  Scoring on the device is the
+ * cyc_nbmodel_* object below.
  *
  * workspaceBytes (0: 256 MiB) bounds the device workspace: the aggregate's
  * run partials (more launches when it is smaller, never other sums).  It
@@ -812,6 +812,54 @@ int64_t cyc_nb_classes_per_pass(cyc_nb_plan plan);
 int cyc_nb_aggregate_dev(cyc_nb_plan plan, const double* X, int64_t nrows, const double* y,
                          const double* w, double* sums, int64_t* badRow, int32_t* badRule,
                          void* stream);
+
+/* NaiveBayesModel's predictions over row-major fp64 rows (nrows x
+ * numFeatures), numClasses and modelType as above.
+ *
+ * Operands (device fp64; cycloneml_amd/naive_bayes.py score_operands makes
+ * them on the host, so no log, log1p or exp of the model runs on the device):
+ * b (numClasses), M (numClasses x numFeatures, row-major) and, gaussian only
+ * (else NULL), V (the variances, M's shape) and ls (numClasses, sum_j log
+ * V_cj).  cyc_nbmodel_create copies or packs what it needs and synchronizes
+ * the stream; the caller's arrays are free afterwards.
+ *   multinomial  raw_c = b_c + sum_j x_j M_cj             (b = pi, M = theta)
+ *   complement   t_c = sum_j x_j M_cj (b = 0, M = theta), raw_c = t_c - (max_c
+ *                t + log sum_c exp(t_c - max))
+ *   bernoulli    raw_c = b_c + sum_j x_j M_cj   (b = pi + sum_j L_cj, M = theta
+ *                - L, L = log1p(-exp theta))
+ *   gaussian     raw_c = b_c - (sum_j (x_j - M_cj)^2 / V_cj + ls_c) / 2
+ * In the three linear forms a term with x_j == 0 is skipped (the reference's
+ * sparse dot): 0 times a -inf of M adds nothing, a nonzero x_j gives -inf.
+ *
+ * scorer: 1 the product path (fp64 MFMA b + X M^T; the linear forms with a
+ * finite M only, anything else fails the create), 2 the plain path (one
+ * thread per row and class, j ascending; every model type), 0 auto: the
+ * product where it is allowed.  cyc_nbmodel_path reports the path (1 or 2).
+ *
+ * cyc_nbmodel_score_dev: raw (nrows x numClasses), prob (exp(raw - max) /
+ * sum_c exp(raw_c - max)), pred (nrows; the first index of the largest raw
+ * under >, from class 0, as fp64); any of the three may be NULL, not all.
+ * Rows are checked first in a pass of their own: multinomial and complement
+ * need values >= 0 (a NaN fails), bernoulli exactly 0 or 1, gaussian nothing.
+ * The lowest offending row goes to *badRow (-1 when none; may be NULL) and the
+ * call fails with the aggregate's message; the outputs are then undefined.
+ * The call synchronizes the stream to read the flag (gaussian: it does not).
+ *
+ * Rows go through in chunks of cyc_nbmodel_chunk_rows = workspaceBytes / (8
+ * numClasses) rows (0: 256 MiB; whole 256-row tiles when more than one; at
+ * least 1), whose raw values live in the workspace when raw is NULL.  A
+ * smaller workspace means more launches, never other bits.  Fixed-order sums,
+ * no atomics on doubles: two calls on the same inputs give the same bits. */
+typedef struct cyc_nbmodel_s* cyc_nbmodel;
+
+int cyc_nbmodel_create(int32_t numClasses, int32_t numFeatures, int32_t modelType,
+                       int64_t workspaceBytes, const double* b, const double* M, const double* V,
+                       const double* ls, int32_t scorer, void* stream, cyc_nbmodel* model);
+int cyc_nbmodel_destroy(cyc_nbmodel model);
+int32_t cyc_nbmodel_path(cyc_nbmodel model);
+int64_t cyc_nbmodel_chunk_rows(cyc_nbmodel model);
+int cyc_nbmodel_score_dev(cyc_nbmodel model, const double* X, int64_t nrows, double* raw,
+                          double* prob, double* pred, int64_t* badRow, void* stream);
 
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
