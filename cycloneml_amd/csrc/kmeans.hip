@@ -374,6 +374,18 @@ struct cyc_kmeans_rows_s {
   cyc::DeviceBuffer bNbr, bNbrR;
   int64_t bCalls = 0, bFullRows = 0;   // bounded calls; rows of their full (first) screens
   cyc::kmsums::IncState inc;   // incremental cluster sums (kmeans_sums.hpp)
+  // The row half of the require(norm >= 0) check, kept with the image: the
+  // rows and the norms passed with them are fixed for its lifetime, so the
+  // first Lloyd call's result for (xnorm, n) -- req[1], the lowest row with a
+  // NaN norm (~0: none), and req[4], the bits of xnorm[0] -- stands for the
+  // later calls, which run the centers' half alone (require_check).
+  struct RowVerdict {
+    bool valid = false;
+    const double* xnorm = nullptr;
+    int64_t n = 0;
+    unsigned long long rbad = ~0ull, x0 = 0;
+    bool holds(const double* xn, int64_t rows) const { return valid && xnorm == xn && n == rows; }
+  } verdict;
 };
 
 namespace {
@@ -860,8 +872,21 @@ int prep_all(cyc_kmeans_plan p, cyc_kmeans_rows rows, const double* xnorm, int64
 // (0, m) for the lowest NaN center m > 0, or (0, 1) when center 0 is NaN;
 // with k == 1 there are no statistics and the first point meets center 0;
 // otherwise the first NaN-norm point meets center 0 (norm2 = NaN).
-int require_check(cyc_kmeans_plan p, int64_t n, const double* Xrow0 = nullptr) {
+// verdict (a Lloyd call with a row image): the image's stored row result put
+// in place of the words a call without the row half left at their presets,
+// or, when it does not hold for (xnorm, n), this call's row result stored.
+int require_check(cyc_kmeans_plan p, int64_t n, const double* Xrow0 = nullptr,
+                  cyc_kmeans_rows_s::RowVerdict* verdict = nullptr,
+                  const double* xnorm = nullptr) {
   CYC_HIP(hipEventSynchronize(p->reqEv));
+  if (verdict) {
+    if (verdict->holds(xnorm, n)) {
+      p->reqHost[1] = verdict->rbad;
+      p->reqHost[4] = verdict->x0;
+    } else {
+      *verdict = {true, xnorm, n, p->reqHost[1], p->reqHost[4]};
+    }
+  }
   const unsigned long long cbad = p->reqHost[0], rbad = p->reqHost[1];
   double* v = reinterpret_cast<double*>(p->reqHost + 2);
   if (Xrow0 && n > 0 && cbad == 0 && !(p->k >= 2)) {
@@ -1419,16 +1444,20 @@ int cyc_kmeans_accumulate_dev(cyc_kmeans_plan p, const double* X, const double* 
     // screen uses them
     ScreenSetup ss;
     if ((rc = screen_setup(p, rows, n, X, nullptr, C, cnorm, false, ss))) return rc;
+    // the rows' half of the require check: once per image (RowVerdict)
+    const bool rowsChecked = rows && rows->verdict.holds(xnorm, n);
+    const double* reqNorm = rowsChecked ? nullptr : xnorm;
+    const int64_t reqRows = rowsChecked ? 0 : n;
     if (fused) {
       bool carry = false;
       if (useBnd && (rc = bounds_reserve(p, rows, n, st, carry))) return rc;
-      if ((rc = prep_all(p, rows, xnorm, n, C, cnorm, useBnd, carry, &ss, st))) return rc;
+      if ((rc = prep_all(p, rows, reqNorm, reqRows, C, cnorm, useBnd, carry, &ss, st))) return rc;
       if (useBnd) {
         if ((rc = bounds_lists(p, rows, xnorm, n, st, bd, carry, true))) return rc;
         assign = (int32_t*)rows->bAssign.ptr;
       }
     } else {
-      if ((rc = require_enqueue(p, C, xnorm, n, st))) return rc;
+      if ((rc = require_enqueue(p, C, reqNorm, reqRows, st))) return rc;
       if ((rc = do_stats(p, C, st))) return rc;
       if (useBnd) {
         if ((rc = bounds_prepare(p, rows, C, xnorm, n, st, bd))) return rc;
@@ -1458,7 +1487,7 @@ int cyc_kmeans_accumulate_dev(cyc_kmeans_plan p, const double* X, const double* 
     if ((rc = cyc::kmsums::inc_accumulate(p->sort, rows->inc, X, xnorm, assign, n, d, k, C, sums,
                                           wsum, cost_sum, st)))
       return rc;
-    rc = require_check(p, n, approxNorm ? X : nullptr);
+    rc = require_check(p, n, approxNorm ? X : nullptr, &rows->verdict, xnorm);
     rows->inc.valid = rc == CYC_OK;
     rows->inc.k = k;
     return rc;
@@ -1485,7 +1514,9 @@ int cyc_kmeans_accumulate_dev(cyc_kmeans_plan p, const double* X, const double* 
   if ((rc = cyc::kmsums::full_pass(p->sort, X, n, d, k, weights, xnorm, cosm, C, assign, cost, sums,
                                    wsum, cost_sum, st)))
     return rc;
-  return cosm ? cos_check(p) : require_check(p, n, approxNorm ? X : nullptr);
+  return cosm ? cos_check(p)
+              : require_check(p, n, approxNorm ? X : nullptr, rows ? &rows->verdict : nullptr,
+                              xnorm);
 }
 
 int cyc_kmeans_update_dev(cyc_kmeans_plan p, double* C, double* cnorm, const double* sums,

@@ -9,6 +9,9 @@
 //   k_inc_*   the incremental sums of a fit with carried bounds: the state of
 //       the last call updated by the rows that changed cluster, with a device
 //       side check that falls back to the full pass above (the gate).
+//   k_*_gated   the full pass behind the incremental sums' gate as four
+//       launches (nine ungated): the small single-workgroup stages run in the
+//       last workgroup to finish the stage before them (last_arrival).
 //   k_update_centers   centroid = (1/w)*sum, new norm, convergence flag.
 #pragma clang fp contract(off)
 
@@ -134,17 +137,26 @@ __global__ void k_scan_clusters(const int64_t* __restrict__ total, int k,
 // from consecutive tiles land side by side in perm; with consecutive tiles
 // on one XCD their 4-byte writes meet in that XCD's L2 instead of partial
 // lines from eight L2s (the grid is 8 * per blocks; the spare ones leave).
-__global__ void k_scatter(const int32_t* __restrict__ assign, int64_t n, int k,
-                          const int32_t* __restrict__ tileOff, const int64_t* __restrict__ cstart,
-                          int32_t* __restrict__ perm, int64_t tiles, const int* __restrict__ gate) {
-  if (gate && !*gate) return;
+// segOff (the gated form, else null): tileOff holds the offsets inside
+// segments of segT tiles and segOff the segments' own (k_hist_scan_gated).
+__device__ __forceinline__ void scatter_tile(const int32_t* __restrict__ assign, int64_t n, int k,
+                                             const int32_t* __restrict__ tileOff,
+                                             const int64_t* __restrict__ cstart,
+                                             int32_t* __restrict__ perm, int64_t tiles,
+                                             const int32_t* __restrict__ segOff, int segT) {
   extern __shared__ int64_t pos[];
   const int64_t per = ((int64_t)gridDim.x + 7) / 8;
   const int64_t tile = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
   if (tile >= tiles) return;
   const int lane = threadIdx.x;
   const int kb = 32 - __builtin_clz((unsigned)max(k - 1, 1));   // bits of a cluster index
-  for (int c = lane; c < k; c += 64) pos[c] = cstart[c] + tileOff[tile * k + c];
+  if (segOff) {
+    const int64_t seg = tile / segT;
+    for (int c = lane; c < k; c += 64)
+      pos[c] = cstart[c] + segOff[seg * k + c] + tileOff[tile * k + c];
+  } else {
+    for (int c = lane; c < k; c += 64) pos[c] = cstart[c] + tileOff[tile * k + c];
+  }
   __syncthreads();
   const int64_t r0 = tile * kSortTile;
   const int64_t r1 = min<int64_t>(n, r0 + kSortTile);
@@ -178,6 +190,13 @@ __global__ void k_scatter(const int32_t* __restrict__ assign, int64_t n, int k,
     }
     __builtin_amdgcn_wave_barrier();
   }
+}
+
+__global__ void k_scatter(const int32_t* __restrict__ assign, int64_t n, int k,
+                          const int32_t* __restrict__ tileOff, const int64_t* __restrict__ cstart,
+                          int32_t* __restrict__ perm, int64_t tiles, const int* __restrict__ gate) {
+  if (gate && !*gate) return;
+  scatter_tile(assign, n, k, tileOff, cstart, perm, tiles, nullptr, 0);
 }
 
 // Partial sums of up to kChunkRows rows of one cluster, rows in index order
@@ -268,18 +287,15 @@ __global__ __launch_bounds__(256) void k_chunk_sums(
 // total then differs from summing the rows' sequential sqdist values only
 // in rounding order (all terms positive, ~1e-16 relative; the bar is 1e-10),
 // and the pass is a plain HBM stream: 8 rows' loads in flight per thread.
+// One chunk ch < chunkStart[k]; rowsS / red / reda: the workgroup's LDS.
 template <int NJ>
-__global__ __launch_bounds__(256) void k_chunk_sums_fast(
+__device__ __forceinline__ void chunk_sums_fast_one(
     const double* __restrict__ X, int d, const double* __restrict__ w,
     const double* __restrict__ C, const int32_t* __restrict__ perm,
     const int64_t* __restrict__ cstart, const int64_t* __restrict__ chunkStart, int k,
     double* __restrict__ part, double* __restrict__ pw, double* __restrict__ pc,
-    const double* __restrict__ xnorm, double* __restrict__ pa, const int* __restrict__ gate) {
-  __shared__ int32_t rowsS[kChunkRows];
-  __shared__ double red[256], reda[256];
-  if (gate && !*gate) return;
-  const int64_t ch = blockIdx.x;
-  if (ch >= chunkStart[k]) return;
+    const double* __restrict__ xnorm, double* __restrict__ pa, const int64_t ch, int32_t* rowsS,
+    double* red, double* reda) {
   int lo = 0, hi = k;
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
@@ -362,6 +378,43 @@ __global__ __launch_bounds__(256) void k_chunk_sums_fast(
   }
 }
 
+template <int NJ>
+__global__ __launch_bounds__(256) void k_chunk_sums_fast(
+    const double* __restrict__ X, int d, const double* __restrict__ w,
+    const double* __restrict__ C, const int32_t* __restrict__ perm,
+    const int64_t* __restrict__ cstart, const int64_t* __restrict__ chunkStart, int k,
+    double* __restrict__ part, double* __restrict__ pw, double* __restrict__ pc,
+    const double* __restrict__ xnorm, double* __restrict__ pa, const int* __restrict__ gate) {
+  __shared__ int32_t rowsS[kChunkRows];
+  __shared__ double red[256], reda[256];
+  if (gate && !*gate) return;
+  const int64_t ch = blockIdx.x;
+  if (ch >= chunkStart[k]) return;
+  chunk_sums_fast_one<NJ>(X, d, w, C, perm, cstart, chunkStart, k, part, pw, pc, xnorm, pa, ch,
+                          rowsS, red, reda);
+}
+
+// The gated form: a grid bounded by the device strides over the chunks, so a
+// closed gate costs the same at every n.  Each chunk writes its own part /
+// pw / pc / pa slot as above, whichever workgroup computes it.
+template <int NJ>
+__global__ __launch_bounds__(256) void k_chunk_sums_fast_gated(
+    const double* __restrict__ X, int d, const double* __restrict__ C,
+    const int32_t* __restrict__ perm, const int64_t* __restrict__ cstart,
+    const int64_t* __restrict__ chunkStart, int k, double* __restrict__ part,
+    double* __restrict__ pw, double* __restrict__ pc, const double* __restrict__ xnorm,
+    double* __restrict__ pa, const int* __restrict__ gate) {
+  __shared__ int32_t rowsS[kChunkRows];
+  __shared__ double red[256], reda[256];
+  if (!*gate) return;
+  const int64_t chunks = chunkStart[k];
+  for (int64_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+    chunk_sums_fast_one<NJ>(X, d, nullptr, C, perm, cstart, chunkStart, k, part, pw, pc, xnorm, pa,
+                            ch, rowsS, red, reda);
+    __syncthreads();   // thread 0 has read red / reda / rowsS
+  }
+}
+
 // Same without the fused cost (d > 1024): costs come from k_row_cost.
 __global__ void k_chunk_sums_nocost(const double* __restrict__ X, int d,
                                     const double* __restrict__ w,
@@ -409,14 +462,15 @@ __global__ void k_chunk_sums_nocost(const double* __restrict__ X, int d,
 // Fold a cluster's chunks in chunk order and add into the caller's sums.
 // fS / fW / fA (optional, the incremental sums' state): the cluster's own
 // sums, weight and sum of w |x| (from pa) stored besides.
-__global__ void k_reduce_clusters(const double* __restrict__ part, const double* __restrict__ pw,
-                                  const double* __restrict__ pc,
-                                  const int64_t* __restrict__ chunkStart, int d,
-                                  double* __restrict__ sums, double* __restrict__ wsum,
-                                  double* __restrict__ ccost, const double* __restrict__ pa,
-                                  double* __restrict__ fS, double* __restrict__ fW,
-                                  double* __restrict__ fA, const int* __restrict__ gate) {
-  if (gate && !*gate) return;
+__device__ __forceinline__ void reduce_cluster(const double* __restrict__ part,
+                                               const double* __restrict__ pw,
+                                               const double* __restrict__ pc,
+                                               const int64_t* __restrict__ chunkStart, int d,
+                                               double* __restrict__ sums,
+                                               double* __restrict__ wsum, double* ccost,
+                                               const double* __restrict__ pa,
+                                               double* __restrict__ fS, double* __restrict__ fW,
+                                               double* __restrict__ fA) {
   const int c = blockIdx.x;
   const int64_t a = chunkStart[c], b = chunkStart[c + 1];
   if (a == b) {
@@ -470,10 +524,19 @@ __global__ void k_reduce_clusters(const double* __restrict__ part, const double*
   }
 }
 
-// Single block, fixed-shape tree: cost_sum += sum_c ccost[c].
-__global__ void k_cost_total(const double* __restrict__ ccost, int k, double* __restrict__ out,
-                             const int* __restrict__ gate) {
+__global__ void k_reduce_clusters(const double* __restrict__ part, const double* __restrict__ pw,
+                                  const double* __restrict__ pc,
+                                  const int64_t* __restrict__ chunkStart, int d,
+                                  double* __restrict__ sums, double* __restrict__ wsum,
+                                  double* __restrict__ ccost, const double* __restrict__ pa,
+                                  double* __restrict__ fS, double* __restrict__ fW,
+                                  double* __restrict__ fA, const int* __restrict__ gate) {
   if (gate && !*gate) return;
+  reduce_cluster(part, pw, pc, chunkStart, d, sums, wsum, ccost, pa, fS, fW, fA);
+}
+
+// Fixed-shape tree over 256 threads: cost_sum += sum_c ccost[c].
+__device__ __forceinline__ void cost_total(const double* ccost, int k, double* __restrict__ out) {
   __shared__ double s[256];
   double a = 0.0;
   for (int c = threadIdx.x; c < k; c += 256) a = dadd(a, ccost[c]);
@@ -484,6 +547,177 @@ __global__ void k_cost_total(const double* __restrict__ ccost, int k, double* __
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = dadd(out[0], s[0]);
+}
+
+// Single block.
+__global__ void k_cost_total(const double* __restrict__ ccost, int k, double* __restrict__ out,
+                             const int* __restrict__ gate) {
+  if (gate && !*gate) return;
+  cost_total(ccost, k, out);
+}
+
+// ------------------------------------------------ the gated full pass
+// The full pass behind inc_accumulate's gate runs in few of a fit's calls,
+// but its launches are enqueued in all of them (the host cannot read the
+// gate without draining the stream), so it is four launches there, each of
+// which ends on a closed gate: k_hist_scan_gated, k_scatter_gated,
+// k_chunk_sums_fast_gated, k_reduce_cost_gated.  The single-workgroup stages
+// between the ungated pass's kernels run in the last workgroup to finish the
+// stage before them; no workgroup waits for another.  Same results as the
+// ungated pass: the integer stages are exact in any grouping, every fp64
+// fold keeps its operands' order.
+
+// True (in every thread) in the last of `total` workgroups to arrive at
+// *ticket, which it zeroes again for the next call; that workgroup then sees
+// what the others stored before arriving (an agent-scope release before the
+// ticket, an acquire after it: the XCDs' L2s are not coherent).  Data handed
+// over this way is read through pointers that are not const __restrict__.
+__device__ __forceinline__ bool last_arrival(unsigned int* ticket, unsigned int total,
+                                             int* lastLds) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int t =
+        __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = t + 1 == total;
+    if (last) {
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *lastLds = last;
+  }
+  __syncthreads();
+  return *lastLds != 0;
+}
+
+// Rows t0..t1 of a[t * k + c] replaced by their exclusive running sums down
+// each column c (256 threads over the columns), done(c, the column's sum).
+// Four columns by eight rows of loads in flight per thread.
+template <class T, class F>
+__device__ __forceinline__ void scan_columns(int32_t* a, int t0, int t1, int k, F&& done) {
+  constexpr int CQ = 4, TB = 8;
+  for (int cb = threadIdx.x; cb < k; cb += 256 * CQ) {
+    T run[CQ];
+#pragma unroll
+    for (int u = 0; u < CQ; ++u) run[u] = 0;
+    for (int t = t0; t < t1; t += TB) {
+      int32_t h[CQ][TB];
+#pragma unroll
+      for (int u = 0; u < CQ; ++u)
+#pragma unroll
+        for (int v = 0; v < TB; ++v) {
+          const int c = cb + 256 * u;
+          h[u][v] = (c < k && t + v < t1) ? a[(int64_t)(t + v) * k + c] : 0;
+        }
+#pragma unroll
+      for (int u = 0; u < CQ; ++u)
+#pragma unroll
+        for (int v = 0; v < TB; ++v) {
+          const int c = cb + 256 * u;
+          if (c < k && t + v < t1) {
+            a[(int64_t)(t + v) * k + c] = (int32_t)run[u];
+            run[u] += h[u][v];
+          }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < CQ; ++u)
+      if (cb + 256 * u < k) done(cb + 256 * u, run[u]);
+  }
+}
+
+constexpr int kTicketWords = 128;  // [0] the segments', [1 + s] segment s's tiles', [127] the folds'
+static_assert(kScanSegs + 1 < kTicketWords - 1, "one ticket per scan segment");
+
+// k_hist, then per segment of segT tiles (the last of its tiles' workgroups)
+// k_scan_seg and k_scan_apply's walk in one -- the tiles' offsets inside the
+// segment, in place, and the segment's sums; k_scatter_gated adds the
+// segment's own offset -- then (the last segment's workgroup) k_scan_segoff
+// and k_scan_clusters.
+__global__ __launch_bounds__(256) void k_hist_scan_gated(
+    const int32_t* __restrict__ assign, int64_t n, int k, int tiles, int segT, int segs,
+    int32_t* hist, int32_t* segsum, int64_t* total, int64_t* __restrict__ cstart,
+    int64_t* __restrict__ chunkStart, unsigned int* tickets, const int* __restrict__ gate) {
+  if (!*gate) return;
+  extern __shared__ int32_t cnt[];
+  __shared__ int lastS;
+  __shared__ int64_t s_rows[256], s_chunks[256];
+  const int tid = threadIdx.x;
+  for (int c = tid; c < k; c += 256) cnt[c] = 0;
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * kSortTile;
+  const int64_t r1 = min<int64_t>(n, r0 + kSortTile);
+  for (int64_t r = r0 + tid; r < r1; r += 256) atomicAdd(&cnt[assign[r]], 1);
+  __syncthreads();
+  for (int c = tid; c < k; c += 256) hist[(int64_t)blockIdx.x * k + c] = cnt[c];
+  const int seg = (int)blockIdx.x / segT;
+  const int t0 = seg * segT, t1 = min(tiles, t0 + segT);
+  if (!last_arrival(&tickets[1 + seg], (unsigned)(t1 - t0), &lastS)) return;
+  scan_columns<int32_t>(hist, t0, t1, k,
+                        [&](int c, int32_t sum) { segsum[(int64_t)seg * k + c] = sum; });
+  if (!last_arrival(&tickets[0], (unsigned)segs, &lastS)) return;
+  scan_columns<int64_t>(segsum, 0, segs, k, [&](int c, int64_t sum) { total[c] = sum; });
+  __syncthreads();
+  // k_scan_clusters over 256 threads
+  const int per = (k + 255) / 256;
+  int64_t rows = 0, chunks = 0;
+  for (int q = 0; q < per; ++q) {
+    const int c = tid * per + q;
+    if (c < k) {
+      rows += total[c];
+      chunks += (total[c] + kChunkRows - 1) / kChunkRows;
+    }
+  }
+  s_rows[tid] = rows;
+  s_chunks[tid] = chunks;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const int64_t a = tid >= off ? s_rows[tid - off] : 0, b = tid >= off ? s_chunks[tid - off] : 0;
+    __syncthreads();
+    s_rows[tid] += a;
+    s_chunks[tid] += b;
+    __syncthreads();
+  }
+  int64_t rbase = tid ? s_rows[tid - 1] : 0, cbase = tid ? s_chunks[tid - 1] : 0;
+  for (int q = 0; q < per; ++q) {
+    const int c = tid * per + q;
+    if (c < k) {
+      cstart[c] = rbase;
+      chunkStart[c] = cbase;
+      rbase += total[c];
+      cbase += (total[c] + kChunkRows - 1) / kChunkRows;
+    }
+  }
+  if (tid == 255) {
+    cstart[k] = s_rows[255];
+    chunkStart[k] = s_chunks[255];
+  }
+}
+
+__global__ void k_scatter_gated(const int32_t* __restrict__ assign, int64_t n, int k,
+                                const int32_t* __restrict__ tileOff,
+                                const int64_t* __restrict__ cstart, int32_t* __restrict__ perm,
+                                int64_t tiles, const int32_t* __restrict__ segOff, int segT,
+                                const int* __restrict__ gate) {
+  if (!*gate) return;
+  scatter_tile(assign, n, k, tileOff, cstart, perm, tiles, segOff, segT);
+}
+
+// k_reduce_clusters, then k_cost_total in the last cluster's workgroup to finish.
+__global__ __launch_bounds__(256) void k_reduce_cost_gated(
+    const double* __restrict__ part, const double* __restrict__ pw, const double* __restrict__ pc,
+    const int64_t* __restrict__ chunkStart, int d, int k, double* __restrict__ sums,
+    double* __restrict__ wsum, double* ccost, const double* __restrict__ pa,
+    double* __restrict__ fS, double* __restrict__ fW, double* __restrict__ fA,
+    double* __restrict__ costSum, unsigned int* ticket, const int* __restrict__ gate) {
+  if (!*gate) return;
+  __shared__ int lastS;
+  reduce_cluster(part, pw, pc, chunkStart, d, sums, wsum, ccost, pa, fS, fW, fA);
+  if (!last_arrival(ticket, (unsigned)k, &lastS)) return;
+  cost_total(ccost, k, costSum);
 }
 
 // ------------------------------------------------- incremental cluster sums
@@ -1003,14 +1237,34 @@ int sort_clusters(SortScratch& s, const int32_t* assign, int64_t n, int d, int k
       (rc = s.ccost.reserve(sizeof(double) * (size_t)k)))
     return rc;
   int32_t* hist = (int32_t*)s.hist.ptr;
+  const int segT = (tiles + std::min(kScanSegs, tiles) - 1) / std::min(kScanSegs, tiles);
+  const int segs = (tiles + segT - 1) / segT;
+  if ((rc = s.segsum.reserve(sizeof(int32_t) * (size_t)segs * k))) return rc;
+  int32_t* segsum = (int32_t*)s.segsum.ptr;
+  if (gate) {
+    // two launches (the gated full pass above); the tickets are zero between
+    // calls: zeroed when allocated, then by their last arrivals
+    const void* had = s.tickets.ptr;
+    const int hadDev = s.tickets.device;
+    if ((rc = s.tickets.reserve(sizeof(unsigned int) * kTicketWords))) return rc;
+    if (s.tickets.ptr != had || s.tickets.device != hadDev)
+      CYC_HIP(hipMemsetAsync(s.tickets.ptr, 0, sizeof(unsigned int) * kTicketWords, st));
+    hipLaunchKernelGGL(k_hist_scan_gated, dim3(tiles), dim3(256), sizeof(int32_t) * k, st, assign,
+                       n, k, tiles, segT, segs, hist, segsum, (int64_t*)s.total.ptr,
+                       (int64_t*)s.cstart.ptr, (int64_t*)s.chunkStart.ptr,
+                       (unsigned int*)s.tickets.ptr, gate);
+    CYC_LAUNCH_CHECK("k_hist_scan_gated");
+    hipLaunchKernelGGL(k_scatter_gated, dim3((unsigned)(8 * (((int64_t)tiles + 7) / 8))), dim3(64),
+                       sizeof(int64_t) * k, st, assign, n, k, (const int32_t*)hist,
+                       (const int64_t*)s.cstart.ptr, (int32_t*)s.perm.ptr, (int64_t)tiles,
+                       (const int32_t*)segsum, segT, gate);
+    CYC_LAUNCH_CHECK("k_scatter_gated");
+    return CYC_OK;
+  }
   hipLaunchKernelGGL(k_hist, dim3(tiles), dim3(256), sizeof(int32_t) * k, st, assign, n, k, hist,
                      gate);
   CYC_LAUNCH_CHECK("k_hist");
   {
-    const int segT = (tiles + std::min(kScanSegs, tiles) - 1) / std::min(kScanSegs, tiles);
-    const int segs = (tiles + segT - 1) / segT;
-    if ((rc = s.segsum.reserve(sizeof(int32_t) * (size_t)segs * k))) return rc;
-    int32_t* segsum = (int32_t*)s.segsum.ptr;
     hipLaunchKernelGGL(k_scan_seg, dim3((unsigned)((k + 63) / 64), (unsigned)segs), dim3(64), 0, st,
                        (const int32_t*)hist, tiles, k, segT, segsum, gate);
     CYC_LAUNCH_CHECK("k_scan_seg");
@@ -1057,7 +1311,15 @@ int full_pass(SortScratch& s, const double* X, int64_t n, int d, int k, const do
     // no per-row costs, d <= 1024: k_chunk_sums_fast (and the incremental
     // state's sum of w |x| into pa); per-row costs wanted: k_chunk_sums;
     // d > 1024: the costs were computed first (k_row_cost)
-    if (!cost && nj <= 4)
+    if (gate && inc && !cost && !weights && nj <= 4)
+      with_nj(nj, [&](auto NJ) {
+        // the gated form: a grid of 8 workgroups per CU strides over the chunks
+        const dim3 bounded((unsigned)std::min<int64_t>(maxChunks, 8 * (int64_t)cyc::device_cus()));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chunk_sums_fast_gated<decltype(NJ)::value>), bounded,
+                           dim3(256), 0, st, X, d, C, perm, cstart, chunkStart, k, part, pw, pc,
+                           xnorm, pa, gate);
+      });
+    else if (!cost && nj <= 4)
       with_nj(nj, [&](auto NJ) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chunk_sums_fast<decltype(NJ)::value>), grid,
                            dim3(256), 0, st, X, d, weights, C, perm, cstart, chunkStart, k, part,
@@ -1073,6 +1335,15 @@ int full_pass(SortScratch& s, const double* X, int64_t n, int d, int k, const do
       hipLaunchKernelGGL(k_chunk_sums_nocost, grid, dim3(256), 0, st, X, d, weights,
                          (const double*)cost, perm, cstart, chunkStart, k, part, pw, pc);
     CYC_LAUNCH_CHECK("k_chunk_sums");
+  }
+  if (gate && inc && !cosine) {
+    hipLaunchKernelGGL(k_reduce_cost_gated, dim3(k), dim3(256), 0, st, (const double*)part,
+                       (const double*)pw, (const double*)pc, chunkStart, d, k, sums, wsum,
+                       (double*)s.ccost.ptr, (const double*)pa, (double*)inc->S.ptr,
+                       (double*)inc->W.ptr, (double*)inc->A.ptr, cost_sum,
+                       (unsigned int*)s.tickets.ptr + (kTicketWords - 1), gate);
+    CYC_LAUNCH_CHECK("k_reduce_cost_gated");
+    return CYC_OK;
   }
   hipLaunchKernelGGL(k_reduce_clusters, dim3(k), dim3(256), 0, st, (const double*)part,
                      (const double*)pw, (const double*)pc, chunkStart, d, sums, wsum,

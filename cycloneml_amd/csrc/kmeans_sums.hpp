@@ -20,9 +20,10 @@ constexpr int kMaxK = 8192;       // LDS histogram bound for the sort
 // Scratch of the sort and the chunk sums, owned by the plan: per-tile
 // histograms, per-cluster totals, cluster and chunk offsets (k + 1 each),
 // the row permutation, the chunks' partial sums / weights / costs, the
-// per-cluster costs and the scan's segment sums.
+// per-cluster costs and the scan's segment sums; tickets: the arrival
+// counters of the gated full pass (zero between calls).
 struct SortScratch {
-  DeviceBuffer hist, total, cstart, chunkStart, perm, part, pw, pc, ccost, segsum;
+  DeviceBuffer hist, total, cstart, chunkStart, perm, part, pw, pc, ccost, segsum, tickets;
 };
 
 // Incremental cluster sums (k_inc_*; with the carried bounds, unit weights,
@@ -41,7 +42,8 @@ struct IncState {
 // Counting sort of rows 0..n by assign[] into s.perm (stable: row order kept
 // within a cluster), with cstart (k + 1 cluster offsets) and chunkStart
 // (k + 1 offsets of kChunkRows-row chunks); part / pw / pc reserved for
-// maxChunks chunks of d columns.  gate (optional, device): skipped when 0.
+// maxChunks chunks of d columns.  gate (optional, device): skipped when 0,
+// and two launches instead of six.
 int sort_clusters(SortScratch& s, const int32_t* assign, int64_t n, int d, int k, hipStream_t st,
                   int64_t& maxChunks, const int* gate = nullptr);
 
@@ -50,7 +52,8 @@ int sort_clusters(SortScratch& s, const int32_t* assign, int64_t n, int d, int k
 // computed by the chunk sums, d <= 1024; required beyond, and for cosine).
 // cosine: sums of x / |x| with xnorm = |x|.  gate + inc (both or neither):
 // the pass runs only when gate[0] != 0 and also resets inc's state from the
-// clusters' sums (unit weights, no costs, d <= 1024; xnorm = |x|).
+// clusters' sums (unit weights, no costs, d <= 1024; xnorm = |x|), in four
+// launches that each end on a closed gate (nine ungated).
 int full_pass(SortScratch& s, const double* X, int64_t n, int d, int k, const double* weights,
               const double* xnorm, bool cosine, const double* C, const int32_t* assign,
               double* cost, double* sums, double* wsum, double* cost_sum, hipStream_t st,

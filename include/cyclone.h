@@ -108,7 +108,13 @@ int cyc_kmeans_stats_dev(cyc_kmeans_plan plan, const double* C, double* stats_ou
  * per (64-padded) element + 8 bytes per row.  Built once from X (n x d device
  * rows); X must not change while the image is used.  For d > 512 the image is
  * empty and the calls below use the bf16 / fp64 screens instead.  Passing the
- * image is optional everywhere (NULL = no i8 tier). */
+ * image is optional everywhere (NULL = no i8 tier).
+ * The norms passed with an image (xnorm of cyc_kmeans_accumulate_dev) are
+ * fixed for its lifetime, as its rows are: the first accumulate call with a
+ * given (xnorm pointer, n) checks the rows' norms for the reference's
+ * require(norm >= 0), the image keeps that result, and later calls with the
+ * same pointer and n check the centers alone (same message on every call).
+ * Norms at another address are checked afresh. */
 typedef struct cyc_kmeans_rows_s* cyc_kmeans_rows;
 int cyc_kmeans_rows_create(cyc_kmeans_plan plan, const double* X, int64_t n, void* stream,
                            cyc_kmeans_rows* rows);
