@@ -1,5 +1,5 @@
 // binary_rows.hpp -- the per-row margin and epilogue shared by the binary
-// block aggregators' kernels (logistic.hip: dense / CSR / CSC paths;
+// block aggregators' kernels (logistic_binary.hip: dense / CSR / CSC paths;
 // tiles.hip: the row-block x column-tile layout).
 #pragma once
 #pragma clang fp contract(off)

@@ -1,5 +1,5 @@
 // tiles.hpp -- internal interface of the row-block x column-tile layout
-// (tiles.hip) for the binary block aggregators (logistic.hip).
+// (tiles.hip) for the binary block aggregators (logistic_binary.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -262,27 +262,22 @@ def _download(t):
     return torch.empty(t.numel(), dtype=torch.float64).copy_(st).numpy()
 
 
-def _logistic_plan(F, C, fit_intercept, fit_with_mean, device, hinge=False):
-    """Plans own device scratch; one per shape and device, reused across the
-    aggregators RDDLossFunction creates every evaluation."""
-    key = (int(F), int(C), bool(fit_intercept), bool(fit_with_mean), str(device), bool(hinge))
+def _plan(key, create, *args):
+    """Plans own device scratch; one per key (kind, shape, constants and
+    device), reused across the aggregators RDDLossFunction creates every
+    evaluation.  `create` names the C constructor, `args` are its arguments
+    before the handle."""
     p = _PLANS.get(key)
     if p is None:
-        p = _PLANS[key] = _LogisticPlan(F, C, fit_intercept, fit_with_mean, hinge)
+        p = _PLANS[key] = _LogisticPlan(create, *args)
     return p
 
 
 class _LogisticPlan:
-    def __init__(self, F, C, fit_intercept, fit_with_mean, hinge=False):
+    def __init__(self, create, *args):
         self._lib = N.load()
         h = ctypes.c_void_p()
-        if hinge:
-            N.check(self._lib.cyc_hinge_plan_create(int(F), int(bool(fit_intercept)),
-                                                    ctypes.byref(h)))
-        else:
-            N.check(self._lib.cyc_logistic_plan_create(int(F), int(C), int(bool(fit_intercept)),
-                                                       int(bool(fit_with_mean)),
-                                                       ctypes.byref(h)))
+        N.check(getattr(self._lib, create)(*args, ctypes.byref(h)))
         self.handle = h
 
     def __del__(self):
@@ -366,258 +361,192 @@ def _check_block(agg, block):
             f"instance weights {'[' + ','.join(map(str, w)) + ']'} has to be >= 0.0")
 
 
-def _tiles_add(agg, block, stream, inverseStd=None):
-    """The binary aggregators' add over a block's SparseTiles layout
-    (cyc_binary_add_tiles_dev; the plan carries the loss kind)."""
-    N.check(N.load().cyc_binary_add_tiles_dev(
-        agg._plan.handle, block.tiles.handle, N.ptr(block.labels), N.ptr(block.weights),
-        N.ptr(agg.coef), N.ptr(inverseStd), N.ptr(agg.scaledMean),
-        N.ptr(agg.gradientSumArray), N.ptr(agg._loss_sum), N.ptr(agg._weight_sum),
-        N.stream_handle(stream)))
-    return agg
+class _BinaryBlockAggregator(DifferentiableLossAggregator):
+    """What the five binary block aggregators share: the coefficient and
+    scaledMean upload, the plan, and one `add` over a block's tiles layout,
+    CSR rows or dense rows.  A subclass names its two C entry points and
+    says whether inverseStd follows the coefficients in their arguments."""
+
+    _dense_dev = _csr_dev = None
+    _pass_inverse_std = False
+
+    @staticmethod
+    def _require_dense(coefficients, end=".)"):
+        if not isinstance(coefficients, (np.ndarray, list, tuple)) and not _torch().is_tensor(
+                coefficients):
+            raise N.IllegalArgumentException(
+                f"coefficients only supports dense vector but got type {type(coefficients)}{end}")
+
+    @staticmethod
+    def _require_scaled_mean(scaledMean, numFeatures):
+        if scaledMean is None or len(scaledMean) != numFeatures:
+            raise N.IllegalArgumentException(
+                "requirement failed: scaled means is required when center the vectors")
+
+    def _upload_coef(self, coefficients, device):
+        torch = _torch()
+        self.coef = _upload(coefficients, device) \
+            if not torch.is_tensor(coefficients) else coefficients.to(device, torch.float64)
+        self.dim = int(self.coef.shape[0])
+
+    def _setup(self, scaledMean, device, key, create, *args):
+        """scaledMean on the device, the cached plan, the zeroed state."""
+        self.scaledMean = _dev_vector(scaledMean, device)
+        self._plan = _plan(key + (str(device),), create, self.numFeatures, *args)
+        self._init_state(device)
+
+    def _check(self, block):
+        _check_block(self, block)
+
+    def add(self, block: DeviceInstanceBlock, stream=None):
+        """The aggregator's add over every block of the shard."""
+        self._check(block)
+        lib = N.load()
+        s = N.stream_handle(stream)
+        inv = (N.ptr(self.inverseStd),) if self._pass_inverse_std else ()
+        state = (N.ptr(self.scaledMean), N.ptr(self.gradientSumArray), N.ptr(self._loss_sum),
+                 N.ptr(self._weight_sum))
+        if block.is_sparse and block.tiles is not None:
+            # cyc_binary_add_tiles_dev serves every kind (the plan carries it)
+            N.check(lib.cyc_binary_add_tiles_dev(
+                self._plan.handle, block.tiles.handle, N.ptr(block.labels), N.ptr(block.weights),
+                N.ptr(self.coef), N.ptr(self.inverseStd if self._pass_inverse_std else None),
+                *state, s))
+        elif block.is_sparse:
+            N.check(getattr(lib, self._csr_dev)(
+                self._plan.handle, N.ptr(block.rowptr), N.ptr(block.colidx), N.ptr(block.values),
+                N.ptr(block.labels), N.ptr(block.weights), block.size, N.ptr(self.coef), *inv,
+                *state, block.csc, s))
+        else:
+            N.check(getattr(lib, self._dense_dev)(
+                self._plan.handle, N.ptr(block.X), N.ptr(block.labels), N.ptr(block.weights),
+                block.size, N.ptr(self.coef), *inv, *state, s))
+        return self
 
 
-class BinaryLogisticBlockAggregator(DifferentiableLossAggregator):
+class BinaryLogisticBlockAggregator(_BinaryBlockAggregator):
     """BinaryLogisticBlockAggregator(bcInverseStd, bcScaledMean, fitIntercept,
-    fitWithMean)(bcCoefficients)."""
+    fitWithMean)(bcCoefficients)
+    (ml/optim/aggregator/BinaryLogisticBlockAggregator.scala:41-146)."""
+
+    _dense_dev = "cyc_binary_logistic_add_dense_dev"
+    _csr_dev = "cyc_binary_logistic_add_csr_dev"
 
     def __init__(self, inverseStd, scaledMean, fitIntercept, fitWithMean, coefficients,
                  device="cuda"):
-        torch = _torch()
         inverseStd = np.asarray(inverseStd, dtype=np.float64)
         if fitWithMean:
             if not fitIntercept:
                 raise N.IllegalArgumentException(
                     "requirement failed: for training without intercept, should not center "
                     "the vectors")
-            if scaledMean is None or len(scaledMean) != len(inverseStd):
-                raise N.IllegalArgumentException(
-                    "requirement failed: scaled means is required when center the vectors")
-        if not isinstance(coefficients, (np.ndarray, list, tuple)) and not torch.is_tensor(
-                coefficients):
-            raise N.IllegalArgumentException(
-                f"coefficients only supports dense vector but got type {type(coefficients)}.)")
+            self._require_scaled_mean(scaledMean, len(inverseStd))
+        self._require_dense(coefficients)
         self.numFeatures = len(inverseStd)
         self.fitIntercept, self.fitWithMean = bool(fitIntercept), bool(fitWithMean)
-        self.coef = _upload(coefficients, device) \
-            if not torch.is_tensor(coefficients) else coefficients.to(device, torch.float64)
-        self.dim = int(self.coef.shape[0])
-        self.scaledMean = _dev_vector(scaledMean, device)
-        self._plan = _logistic_plan(self.numFeatures, 1, self.fitIntercept, self.fitWithMean,
-                                    device)
-        self._init_state(device)
-
-    def add(self, block: DeviceInstanceBlock, stream=None):
-        """BinaryLogisticBlockAggregator.scala:81-145 over every block of the shard."""
-        _check_block(self, block)
-        lib = N.load()
-        s = N.stream_handle(stream)
-        if block.is_sparse and block.tiles is not None:
-            return _tiles_add(self, block, stream)
-        if block.is_sparse:
-            N.check(lib.cyc_binary_logistic_add_csr_dev(
-                self._plan.handle, N.ptr(block.rowptr), N.ptr(block.colidx), N.ptr(block.values),
-                N.ptr(block.labels), N.ptr(block.weights), block.size, N.ptr(self.coef),
-                N.ptr(self.scaledMean), N.ptr(self.gradientSumArray), N.ptr(self._loss_sum),
-                N.ptr(self._weight_sum), block.csc, s))
-        else:
-            N.check(lib.cyc_binary_logistic_add_dense_dev(
-                self._plan.handle, N.ptr(block.X), N.ptr(block.labels), N.ptr(block.weights),
-                block.size, N.ptr(self.coef), N.ptr(self.scaledMean),
-                N.ptr(self.gradientSumArray), N.ptr(self._loss_sum), N.ptr(self._weight_sum), s))
-        return self
+        self._upload_coef(coefficients, device)
+        self._setup(scaledMean, device,
+                    ("logistic", self.numFeatures, 1, self.fitIntercept, self.fitWithMean),
+                    "cyc_logistic_plan_create", 1, int(self.fitIntercept), int(self.fitWithMean))
 
 
-class HingeBlockAggregator(DifferentiableLossAggregator):
+class HingeBlockAggregator(_BinaryBlockAggregator):
     """HingeBlockAggregator(bcInverseStd, bcScaledMean, fitIntercept)(bcCoefficients)
     (ml/optim/aggregator/HingeBlockAggregator.scala:41-141, LinearSVC's loss):
     the binary block kernels with the hinge epilogue; centers whenever it fits
     an intercept."""
 
+    _dense_dev = "cyc_hinge_add_dense_dev"
+    _csr_dev = "cyc_hinge_add_csr_dev"
+
     def __init__(self, inverseStd, scaledMean, fitIntercept, coefficients, device="cuda"):
-        torch = _torch()
         inverseStd = np.asarray(inverseStd, dtype=np.float64)
-        if fitIntercept and (scaledMean is None or len(scaledMean) != len(inverseStd)):
-            raise N.IllegalArgumentException(
-                "requirement failed: scaled means is required when center the vectors")
-        if not isinstance(coefficients, (np.ndarray, list, tuple)) and not torch.is_tensor(
-                coefficients):
-            raise N.IllegalArgumentException(
-                f"coefficients only supports dense vector but got type {type(coefficients)}.)")
+        if fitIntercept:
+            self._require_scaled_mean(scaledMean, len(inverseStd))
+        self._require_dense(coefficients)
         self.numFeatures = len(inverseStd)
         self.fitIntercept = bool(fitIntercept)
-        self.coef = _upload(coefficients, device) \
-            if not torch.is_tensor(coefficients) else coefficients.to(device, torch.float64)
-        self.dim = int(self.coef.shape[0])
-        self.scaledMean = _dev_vector(scaledMean, device)
-        self._plan = _logistic_plan(self.numFeatures, 1, self.fitIntercept, self.fitIntercept,
-                                    device, hinge=True)
-        self._init_state(device)
-
-    def add(self, block: DeviceInstanceBlock, stream=None):
-        """HingeBlockAggregator.scala:81-141 over every block of the shard."""
-        _check_block(self, block)
-        lib = N.load()
-        s = N.stream_handle(stream)
-        if block.is_sparse and block.tiles is not None:
-            return _tiles_add(self, block, stream)
-        if block.is_sparse:
-            N.check(lib.cyc_hinge_add_csr_dev(
-                self._plan.handle, N.ptr(block.rowptr), N.ptr(block.colidx), N.ptr(block.values),
-                N.ptr(block.labels), N.ptr(block.weights), block.size, N.ptr(self.coef),
-                N.ptr(self.scaledMean), N.ptr(self.gradientSumArray), N.ptr(self._loss_sum),
-                N.ptr(self._weight_sum), block.csc, s))
-        else:
-            N.check(lib.cyc_hinge_add_dense_dev(
-                self._plan.handle, N.ptr(block.X), N.ptr(block.labels), N.ptr(block.weights),
-                block.size, N.ptr(self.coef), N.ptr(self.scaledMean),
-                N.ptr(self.gradientSumArray), N.ptr(self._loss_sum), N.ptr(self._weight_sum), s))
-        return self
+        self._upload_coef(coefficients, device)
+        self._setup(scaledMean, device, ("hinge", self.numFeatures, self.fitIntercept),
+                    "cyc_hinge_plan_create", int(self.fitIntercept))
 
 
-class LeastSquaresBlockAggregator(DifferentiableLossAggregator):
+class LeastSquaresBlockAggregator(_BinaryBlockAggregator):
     """LeastSquaresBlockAggregator(bcInverseStd, bcScaledMean, fitIntercept,
     labelStd, labelMean)(bcCoefficients)
     (ml/optim/aggregator/LeastSquaresBlockAggregator.scala:31-101): the binary
     block kernels with the squared-error epilogue; dim = numFeatures."""
 
+    _dense_dev = "cyc_least_squares_add_dense_dev"
+    _csr_dev = "cyc_least_squares_add_csr_dev"
+    _pass_inverse_std = True
+
     def __init__(self, inverseStd, scaledMean, fitIntercept, labelStd, labelMean, coefficients,
                  device="cuda"):
-        torch = _torch()
         if not labelStd > 0.0:
             raise N.IllegalArgumentException(
                 "requirement failed: LeastSquaresBlockAggregator requires the label standard "
                 "deviation to be positive.")
-        if not isinstance(coefficients, (np.ndarray, list, tuple)) and not torch.is_tensor(
-                coefficients):
-            raise N.IllegalArgumentException(
-                f"coefficients only supports dense vector but got type {type(coefficients)}.)")
+        self._require_dense(coefficients)
         inv = np.asarray(inverseStd, dtype=np.float64)
         self.numFeatures = len(inv)
         self.fitIntercept = bool(fitIntercept)
-        self.inverseStd = torch.as_tensor(inv, device=device)
-        self.coef = _upload(coefficients, device) \
-            if not torch.is_tensor(coefficients) else coefficients.to(device, torch.float64)
+        self.inverseStd = _torch().as_tensor(inv, device=device)
+        self._upload_coef(coefficients, device)
         self.dim = self.numFeatures
-        self.scaledMean = _dev_vector(scaledMean, device)
-        key = ("ls", self.numFeatures, self.fitIntercept, float(labelStd), float(labelMean),
-               str(device))
-        self._plan = _PLANS.get(key)
-        if self._plan is None:
-            self._plan = _PLANS[key] = _LeastSquaresPlan(self.numFeatures, self.fitIntercept,
-                                                         labelStd, labelMean)
-        self._init_state(device)
-
-    def add(self, block: DeviceInstanceBlock, stream=None):
-        """LeastSquaresBlockAggregator.scala:70-101 over every block of the shard."""
-        _check_block(self, block)
-        lib = N.load()
-        s = N.stream_handle(stream)
-        if block.is_sparse and block.tiles is not None:
-            return _tiles_add(self, block, stream, self.inverseStd)
-        if block.is_sparse:
-            N.check(lib.cyc_least_squares_add_csr_dev(
-                self._plan.handle, N.ptr(block.rowptr), N.ptr(block.colidx), N.ptr(block.values),
-                N.ptr(block.labels), N.ptr(block.weights), block.size, N.ptr(self.coef),
-                N.ptr(self.inverseStd), N.ptr(self.scaledMean), N.ptr(self.gradientSumArray),
-                N.ptr(self._loss_sum), N.ptr(self._weight_sum), block.csc, s))
-        else:
-            N.check(lib.cyc_least_squares_add_dense_dev(
-                self._plan.handle, N.ptr(block.X), N.ptr(block.labels), N.ptr(block.weights),
-                block.size, N.ptr(self.coef), N.ptr(self.inverseStd), N.ptr(self.scaledMean),
-                N.ptr(self.gradientSumArray), N.ptr(self._loss_sum), N.ptr(self._weight_sum), s))
-        return self
+        self._setup(scaledMean, device,
+                    ("ls", self.numFeatures, self.fitIntercept, float(labelStd), float(labelMean)),
+                    "cyc_least_squares_plan_create", int(self.fitIntercept), float(labelStd),
+                    float(labelMean))
 
 
-class HuberBlockAggregator(DifferentiableLossAggregator):
+class HuberBlockAggregator(_BinaryBlockAggregator):
     """HuberBlockAggregator(bcInverseStd, bcScaledMean, fitIntercept, epsilon)
     (bcParameters) (ml/optim/aggregator/HuberBlockAggregator.scala:41-141):
     the binary block kernels with the Huber epilogue; parameters = linear
     terms, intercept (if fitIntercept), sigma."""
 
+    _dense_dev = "cyc_huber_add_dense_dev"
+    _csr_dev = "cyc_huber_add_csr_dev"
+
     def __init__(self, inverseStd, scaledMean, fitIntercept, epsilon, parameters,
                  device="cuda"):
-        torch = _torch()
         inv = np.asarray(inverseStd, dtype=np.float64)
-        if fitIntercept and (scaledMean is None or len(scaledMean) != len(inv)):
-            raise N.IllegalArgumentException(
-                "requirement failed: scaled means is required when center the vectors")
+        if fitIntercept:
+            self._require_scaled_mean(scaledMean, len(inv))
         self.numFeatures = len(inv)
         self.fitIntercept = bool(fitIntercept)
-        self.coef = _upload(parameters, device) \
-            if not torch.is_tensor(parameters) else parameters.to(device, torch.float64)
-        self.dim = int(self.coef.shape[0])
+        self._upload_coef(parameters, device)
         if self.dim != self.numFeatures + (2 if self.fitIntercept else 1):
             raise N.IllegalArgumentException(
                 f"requirement failed: parameters size {self.dim} does not match numFeatures "
                 f"{self.numFeatures} (+ intercept) + sigma")
-        self.scaledMean = _dev_vector(scaledMean, device)
-        key = ("huber", self.numFeatures, self.fitIntercept, float(epsilon), str(device))
-        self._plan = _PLANS.get(key)
-        if self._plan is None:
-            self._plan = _PLANS[key] = _HuberPlan(self.numFeatures, self.fitIntercept, epsilon)
-        self._init_state(device)
-
-    def add(self, block: DeviceInstanceBlock, stream=None):
-        """HuberBlockAggregator.scala:80-141 over every block of the shard."""
-        _check_block(self, block)
-        lib = N.load()
-        s = N.stream_handle(stream)
-        if block.is_sparse and block.tiles is not None:
-            return _tiles_add(self, block, stream)
-        if block.is_sparse:
-            N.check(lib.cyc_huber_add_csr_dev(
-                self._plan.handle, N.ptr(block.rowptr), N.ptr(block.colidx), N.ptr(block.values),
-                N.ptr(block.labels), N.ptr(block.weights), block.size, N.ptr(self.coef),
-                N.ptr(self.scaledMean), N.ptr(self.gradientSumArray), N.ptr(self._loss_sum),
-                N.ptr(self._weight_sum), block.csc, s))
-        else:
-            N.check(lib.cyc_huber_add_dense_dev(
-                self._plan.handle, N.ptr(block.X), N.ptr(block.labels), N.ptr(block.weights),
-                block.size, N.ptr(self.coef), N.ptr(self.scaledMean),
-                N.ptr(self.gradientSumArray), N.ptr(self._loss_sum), N.ptr(self._weight_sum), s))
-        return self
+        self._setup(scaledMean, device,
+                    ("huber", self.numFeatures, self.fitIntercept, float(epsilon)),
+                    "cyc_huber_plan_create", int(self.fitIntercept), float(epsilon))
 
 
-class _HuberPlan(_LogisticPlan):
-    def __init__(self, F, fit_intercept, epsilon):
-        self._lib = N.load()
-        h = ctypes.c_void_p()
-        N.check(self._lib.cyc_huber_plan_create(int(F), int(bool(fit_intercept)), float(epsilon),
-                                                ctypes.byref(h)))
-        self.handle = h
-
-
-class AFTBlockAggregator(DifferentiableLossAggregator):
+class AFTBlockAggregator(_BinaryBlockAggregator):
     """AFTBlockAggregator(bcScaledMean, fitIntercept)(bcCoefficients)
     (ml/optim/aggregator/AFTBlockAggregator.scala:30-130): the binary block
     kernels with the AFT survival epilogue.  coefficients = F linear terms,
     intercept, log(sigma); a block's `weights` carry the censors, as the
     reference's InstanceBlock does (:97)."""
 
+    _dense_dev = "cyc_aft_add_dense_dev"
+    _csr_dev = "cyc_aft_add_csr_dev"
+
     def __init__(self, scaledMean, fitIntercept, coefficients, device="cuda"):
-        torch = _torch()
-        if not isinstance(coefficients, (np.ndarray, list, tuple)) and not torch.is_tensor(
-                coefficients):
-            raise N.IllegalArgumentException(
-                f"coefficients only supports dense vector but got type {type(coefficients)}.")
-        self.coef = _upload(coefficients, device) \
-            if not torch.is_tensor(coefficients) else coefficients.to(device, torch.float64)
-        self.dim = int(self.coef.shape[0])
+        self._require_dense(coefficients, end=".")
+        self._upload_coef(coefficients, device)
         self.numFeatures = self.dim - 2
         self.fitIntercept = bool(fitIntercept)
-        if self.fitIntercept and (scaledMean is None or len(scaledMean) != self.numFeatures):
-            raise N.IllegalArgumentException(
-                "requirement failed: scaled means is required when center the vectors")
-        self.scaledMean = _dev_vector(scaledMean, device)
-        key = ("aft", self.numFeatures, self.fitIntercept, str(device))
-        self._plan = _PLANS.get(key)
-        if self._plan is None:
-            self._plan = _PLANS[key] = _AFTPlan(self.numFeatures, self.fitIntercept)
-        self._init_state(device)
+        if self.fitIntercept:
+            self._require_scaled_mean(scaledMean, self.numFeatures)
+        self._setup(scaledMean, device, ("aft", self.numFeatures, self.fitIntercept),
+                    "cyc_aft_plan_create", int(self.fitIntercept))
 
-    def add(self, block: DeviceInstanceBlock, stream=None):
-        """AFTBlockAggregator.scala:76-130 over every block of the shard."""
+    def _check(self, block):
         if self.numFeatures != block.numFeatures:
             raise N.IllegalArgumentException(
                 "requirement failed: Dimensions mismatch when adding new instance. Expecting "
@@ -625,40 +554,6 @@ class AFTBlockAggregator(DifferentiableLossAggregator):
         if block.size and bool((block.labels <= 0).any().item()):      # :81
             raise N.IllegalArgumentException(
                 "requirement failed: The lifetime or label should be greater than 0.")
-        lib = N.load()
-        s = N.stream_handle(stream)
-        if block.is_sparse and block.tiles is not None:
-            return _tiles_add(self, block, stream)
-        if block.is_sparse:
-            N.check(lib.cyc_aft_add_csr_dev(
-                self._plan.handle, N.ptr(block.rowptr), N.ptr(block.colidx), N.ptr(block.values),
-                N.ptr(block.labels), N.ptr(block.weights), block.size, N.ptr(self.coef),
-                N.ptr(self.scaledMean), N.ptr(self.gradientSumArray), N.ptr(self._loss_sum),
-                N.ptr(self._weight_sum), block.csc, s))
-        else:
-            N.check(lib.cyc_aft_add_dense_dev(
-                self._plan.handle, N.ptr(block.X), N.ptr(block.labels), N.ptr(block.weights),
-                block.size, N.ptr(self.coef), N.ptr(self.scaledMean),
-                N.ptr(self.gradientSumArray), N.ptr(self._loss_sum), N.ptr(self._weight_sum), s))
-        return self
-
-
-class _AFTPlan(_LogisticPlan):
-    def __init__(self, F, fit_intercept):
-        self._lib = N.load()
-        h = ctypes.c_void_p()
-        N.check(self._lib.cyc_aft_plan_create(int(F), int(bool(fit_intercept)), ctypes.byref(h)))
-        self.handle = h
-
-
-class _LeastSquaresPlan(_LogisticPlan):
-    def __init__(self, F, fit_intercept, label_std, label_mean):
-        self._lib = N.load()
-        h = ctypes.c_void_p()
-        N.check(self._lib.cyc_least_squares_plan_create(int(F), int(bool(fit_intercept)),
-                                                        float(label_std), float(label_mean),
-                                                        ctypes.byref(h)))
-        self.handle = h
 
 
 class MultinomialLogisticBlockAggregator(DifferentiableLossAggregator):
@@ -687,8 +582,10 @@ class MultinomialLogisticBlockAggregator(DifferentiableLossAggregator):
         if self.dim != self.numClasses * fpi:
             raise N.IllegalArgumentException("requirement failed")
         self.scaledMean = _dev_vector(scaledMean, device)
-        self._plan = _logistic_plan(self.numFeatures, self.numClasses, self.fitIntercept,
-                                    self.fitWithMean, device)
+        self._plan = _plan(("logistic", self.numFeatures, self.numClasses, self.fitIntercept,
+                            self.fitWithMean, str(device)), "cyc_logistic_plan_create",
+                           self.numFeatures, self.numClasses, int(self.fitIntercept),
+                           int(self.fitWithMean))
         self._init_state(device)
 
     def add(self, block: DeviceInstanceBlock, stream=None):

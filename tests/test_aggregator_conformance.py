@@ -1,5 +1,6 @@
-"""Conformance of the block aggregators (cycloneml_amd/csrc/logistic.hip,
-binary_rows.hpp, tiles.hip, csc.hip) at their launch and tile edges.
+"""Conformance of the block aggregators (cycloneml_amd/csrc/logistic_binary.hip,
+logistic_multinomial.hip, logistic.hip, binary_rows.hpp, tiles.hip, csc.hip) at
+their launch and tile edges.
 
 Reference: ``ref_add`` below, a vectorised ``np.longdouble`` restatement of the
 six ``add`` operations -- binary logistic, hinge, least squares, Huber, AFT,

@@ -494,6 +494,58 @@ def test_hinge_tiles_large_f_and_plan_kinds(cuda):
     lib.cyc_logistic_plan_destroy(h)
 
 
+def test_binary_entry_points_check_the_plan_kind(cuda):
+    """Every binary add_dense_dev / add_csr_dev entry point against a plan of
+    each of the five kinds (n = 3, F = 3): its own kind's plan succeeds, the
+    four others are refused with the entry point's "the plan is not a ...
+    plan" message."""
+    import ctypes
+    import torch
+    from cycloneml_amd import _native as N
+    lib = N.load()
+    F, n = 3, 3
+    # kind: (plan constructor arguments after F, the entry points' message)
+    kinds = {
+        "binary_logistic": (("cyc_logistic_plan_create", 1, 0, 0),
+                            b"the plan is not a binary logistic plan"),
+        "hinge": (("cyc_hinge_plan_create", 0), b"the plan is not a hinge plan"),
+        "least_squares": (("cyc_least_squares_plan_create", 0, 2.0, 0.5),
+                          b"the plan is not a least squares plan"),
+        "huber": (("cyc_huber_plan_create", 0, 1.35), b"the plan is not a Huber plan"),
+        "aft": (("cyc_aft_plan_create", 0), b"the plan is not an AFT plan"),
+    }
+    t = lambda a, dt=torch.float64: torch.tensor(a, dtype=dt, device=cuda)
+    X = t([[1.0, 0.0, 2.0], [0.0, -1.0, 0.5], [0.25, 0.0, 0.0]])
+    rp, ci = t([0, 2, 4, 5], torch.int64), t([0, 2, 1, 2, 0], torch.int32)
+    vv = t([1.0, 2.0, -1.0, 0.5, 0.25])
+    labels, w = t([1.0, 1.0, 1.0]), t([1.0, 0.5, 1.0])     # labels > 0 (AFT)
+    coef = t([0.1, -0.2, 0.3, 1.0, 0.0])   # F terms, then Huber's sigma = 1, AFT's log sigma = 0
+    inv = t([1.0, 1.0, 1.0])
+    for planKind, ((create, *args), _) in kinds.items():
+        h = ctypes.c_void_p()
+        N.check(getattr(lib, create)(F, *args, ctypes.byref(h)))
+        for kind, (_, message) in kinds.items():
+            extra = (N.ptr(inv),) if kind == "least_squares" else ()
+            state = torch.zeros(F + 4, dtype=torch.float64, device=cuda)
+            tail = (None, N.ptr(state), N.ptr(state[F + 2:]), N.ptr(state[F + 3:]))
+            calls = {
+                "dense": lambda: getattr(lib, f"cyc_{kind}_add_dense_dev")(
+                    h, N.ptr(X), N.ptr(labels), N.ptr(w), n, N.ptr(coef), *extra, *tail, None),
+                "csr": lambda: getattr(lib, f"cyc_{kind}_add_csr_dev")(
+                    h, N.ptr(rp), N.ptr(ci), N.ptr(vv), N.ptr(labels), N.ptr(w), n, N.ptr(coef),
+                    *extra, *tail, None, None),
+            }
+            for layout, call in calls.items():
+                rc, where = call(), (planKind, kind, layout)
+                if kind == planKind:
+                    assert rc == 0, (where, lib.cyc_last_error())
+                else:
+                    assert rc != 0 and message in lib.cyc_last_error(), \
+                        (where, lib.cyc_last_error())
+        torch.cuda.synchronize()
+        lib.cyc_logistic_plan_destroy(h)
+
+
 @pytest.mark.parametrize("sparse", [False, True, "csc", "tiles"])
 @pytest.mark.parametrize("fi", [False, True])
 @pytest.mark.parametrize("n,F", [(1, 3), (257, 17), (3000, 64), (2000, 300)])

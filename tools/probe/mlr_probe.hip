@@ -1,11 +1,12 @@
 // Time k_mlr_margins<7> (multinomial LR margins, C = 100, F = 512) on
-// synthetic rows, built with -DCYC_MLR_PROBE=bits (logistic.hip: 1 = X for
-// chunk 0 only, 2 = no softmax epilogue, 4 = no W DMA) to see which part
-// sets its pace.  Results of modes other than 0 are meaningless.
+// synthetic rows, built with -DCYC_MLR_PROBE=bits (logistic_multinomial.hip,
+// included below as text: 1 = X for chunk 0 only, 2 = no softmax epilogue,
+// 4 = no W DMA) to see which part sets its pace.  Results of modes other than
+// 0 are meaningless.  The shared folds come from libcyclone.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DCYC_MLR_PROBE=1
 //     -I cycloneml_amd/csrc tools/probe/mlr_probe.hip -L cycloneml_amd -lcyclone
 //     -Wl,-rpath,'$ORIGIN/../../cycloneml_amd' -o tools/bin/mlr_m1
-#include "../../cycloneml_amd/csrc/logistic.hip"
+#include "../../cycloneml_amd/csrc/logistic_multinomial.hip"
 
 #ifndef PROBE_NW
 #define PROBE_NW 8
