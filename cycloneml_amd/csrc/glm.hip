@@ -1,7 +1,7 @@
 // glm.hip -- the per-row passes of GeneralizedLinearRegression's IRLS fit on
 // gfx950 (MI355X): ml/regression/GeneralizedLinearRegression.scala
 // (FamilyAndLink.initialize / reweightFunc / fitted, the families' deviance
-// and aic terms) around the WLS aggregate of gramian.hip (k_wls_tiles).
+// and aic terms) around the WLS aggregate of wls.hip (k_wls_tiles).
 //
 // Family and link are two integer codes in the plan, dispatched per row by
 // the __device__ functions below: one kernel per pass and row layout, not

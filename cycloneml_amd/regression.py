@@ -6,7 +6,7 @@ The reference's fit is one treeAggregate whose seqOp
 (WeightedLeastSquares.Aggregator.add) accumulates aaSum, abSum, aSum, bSum,
 bbSum and wSum per instance, then a small solve on the driver.  Here the
 aggregate is one weighted fp64 MFMA syrk over the augmented rows
-z = [a, b, 1.0] (libcyclone's k_wls_tiles, cyc_wls_accumulate_dev): the
+z = [a, b, 1.0] (libcyclone's k_wls_tiles in wls.hip, cyc_wls_accumulate_dev): the
 packed upper triangle U of sum_r w_r z_r z_r^T holds every field.  With
 torch.distributed initialised each rank runs it on its shard and one
 all-reduce of U is the combOp.  `WeightedLeastSquares.solve` is the driver

@@ -50,7 +50,7 @@ int cyc_set_device(int device);
 int cyc_synchronize(void* stream);
 
 /* Measurement hook (bench.py's roofline): while enabled, every launch of a
- * workload's dominant kernel (k_kmeans_assign, k_gram_tiles, k_mlr_margins,
+ * workload's dominant kernel (k_kmeans_assign, k_gram_dma, k_mlr_margins,
  * k_mlr_grad, k_binlog_dense, k_binlog_csr) is bracketed by HIP events on the
  * stream it runs on.  query waits for the recorded events of `kernel`,
  * returns their summed time (ms) and count, and forgets them. */

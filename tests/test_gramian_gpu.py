@@ -62,6 +62,32 @@ def test_gramian_vs_oracle(cuda, n, p):
     np.testing.assert_allclose(U, R, rtol=1e-12)
 
 
+@pytest.mark.parametrize("n,p", [(37, 256), (10001, 130), (15, 2)])
+def test_staged_tiles_even_width(cuda, monkeypatch, n, p):
+    """k_gram_tiles at even widths (CYC_GRAMIAN_KERNEL=tiles, read per call):
+    its 16-byte vector loads, plain and with the mean subtracted.  Two full
+    panels with a ragged last chunk; a ragged second panel with several
+    splits; a panel narrower than one thread's 8 columns."""
+    import torch
+    from cycloneml_amd.linalg import GramianPlan
+    monkeypatch.setenv("CYC_GRAMIAN_KERNEL", "tiles")
+    plan = GramianPlan(p)
+    size = p * (p + 1) // 2
+
+    X = np.random.default_rng(n + p).uniform(0, 1, size=(n, p))
+    U = torch.zeros(size, dtype=torch.float64, device=cuda)
+    plan.accumulate(_dev(X, cuda), U)
+    np.testing.assert_allclose(U.cpu().numpy(), oracle.gramian_partition(X), rtol=1e-12)
+
+    X = np.random.default_rng(p).normal(size=(n, p)) + 3.0
+    mean = X.sum(0) / n
+    U = torch.zeros(size, dtype=torch.float64, device=cuda)
+    plan.accumulate(_dev(X, cuda), U, _dev(mean, cuda))
+    np.testing.assert_allclose(U.cpu().numpy(), oracle.gramian_partition(X, mean),
+                               rtol=1e-10, atol=1e-12)
+    plan.close()
+
+
 @pytest.mark.parametrize("form", ["auto", "centred", "uncentred"])
 @pytest.mark.parametrize("n,p", [(500, 7), (4000, 200), (13, 2), (1001, 130)])
 def test_covariance_vs_oracle(cuda, n, p, form):

@@ -51,10 +51,10 @@ def short_name(full):
         if len(args) >= 3 and args[2] == "true":
             base = "k_screen_cands3_rc"
     if base == "k_gram_dma" and tmpl:
-        # the centred covariance form (MEAN 1 / 2) apart from the plain syrk
-        # (MEAN 0, with or without the riding column sums): bench.py's timer
-        # names
-        if tmpl.split(",")[0].strip() in ("1", "2"):
+        # the centred covariance form (k_gram_dma<1>; <1, ...> in older
+        # profiles) apart from the plain syrk (<0>, or <2> with the riding
+        # column sums): bench.py's timer names
+        if tmpl.rstrip(">").split(",")[0].strip() == "1":
             base = "k_gram_dma_cov"
     return base
 
