@@ -7,6 +7,11 @@ include/cyclone.h); these modules mirror the reference's Scala interfaces.
 __version__ = "0.1.0"
 
 from . import _native  # noqa: F401  (loads nothing until first use)
+from .bisecting_kmeans import (  # noqa: F401
+    BisectingKMeans,
+    BisectingKMeansModel,
+    BKMPlan,
+)
 from .classification import (  # noqa: F401
     MultilayerPerceptronClassificationModel,
     MultilayerPerceptronClassifier,

@@ -202,6 +202,18 @@ SIGNATURES = {
     "cyc_nbmodel_path": (_i32, [_vp]),
     "cyc_nbmodel_chunk_rows": (_i64, [_vp]),
     "cyc_nbmodel_score_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _pi64, _vp]),
+    "cyc_bkm_plan_create": (ctypes.c_int, [_i32, _i64, ctypes.POINTER(_vp)]),
+    "cyc_bkm_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_bkm_tile_rows": (_i64, [_vp]),
+    "cyc_bkm_panel_cols": (_i64, [_vp]),
+    "cyc_bkm_chunk_rows": (_i64, [_vp]),
+    "cyc_bkm_chunks_per_launch": (_i64, [_vp]),
+    "cyc_bkm_max_children": (_i64, [_vp]),
+    # table and the node arrays: host pointers
+    "cyc_bkm_step_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp,
+                                        _vp, _vp, _vp, _i32, _pi64, _pi32, _vp]),
+    "cyc_bkm_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp]),
     "cyc_als_segment": (ctypes.c_int, []),
     "cyc_als_side_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp,
                                            ctypes.POINTER(_vp)]),

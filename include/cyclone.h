@@ -867,6 +867,82 @@ int64_t cyc_nbmodel_chunk_rows(cyc_nbmodel model);
 int cyc_nbmodel_score_dev(cyc_nbmodel model, const double* X, int64_t nrows, double* raw,
                           double* prob, double* pred, int64_t* badRow, void* stream);
 
+/* ------------------------------------------------------ BisectingKMeans
+ * mllib/clustering/BisectingKMeans.scala's inner iteration and
+ * BisectingKMeansModel's descent over row-major fp64 rows (nrows x
+ * numFeatures, nrows < 2^31), Euclidean measure.  The level logic and the tree
+ * are host code (cycloneml_amd/bisecting_kmeans.py).
+ *
+ * State.  Every row has an int32 slot, a compact id of the cluster it sits in
+ * (slot, device, nrows; NULL: every row in slot 0); the caller keeps the slot
+ * <-> node index map.  table (HOST, 3 numSlots int32) holds per slot
+ * (leftNew, rightNew, keepNew): the new slots of the children on offer, -1 for
+ * an absent one, and the new slot of a row that is offered none.  New slots 0
+ * .. numChildren - 1 are the children: row c of centers (numChildren x
+ * numFeatures, device) and cnorm (its Vectors.norm, device).  keepNew is -1 or
+ * >= numChildren; a slot has a child or a keepNew.  numChildren <=
+ * cyc_bkm_max_children.
+ *
+ * cyc_bkm_step_dev writes newSlot (device, nrows; may be slot itself): the
+ * child picked by DistanceMeasure.findClosest (:318-340, no statistics) over
+ * [left, right] with xnorm (device, cyc_row_norms_dev) -- the bound (c.norm -
+ * x.norm)^2 < best decides whether a center's Vectors.sqdist (j ascending,
+ * unfused) is looked at, and it wins only under <, so ties go left -- the only
+ * child when one is on offer, else keepNew.  Only rows with two children on
+ * offer are loaded.  A slot outside [0, numSlots) is never an index: the row
+ * keeps it and the call fails (rule 3).
+ *
+ * Summary (count and sums both non-NULL, device; else both NULL).  Per child
+ * c, ADDED into count (int64, numChildren) and sums (fp64, numChildren (2 +
+ * numFeatures): [wsum | sumSq | sum (numChildren x numFeatures)]): the rows
+ * that picked c, the sum of w, of (xnorm xnorm) w and of w x (w: device, nrows,
+ * or NULL for 1).  Buffers of several calls (or ranks) merge by addition.  sum
+ * is taken in row order within a child: chunks of cyc_bkm_chunk_rows rows,
+ * folded in order; wsum and sumSq by one fixed tree per chunk, the chunks in
+ * order.  The root's summary is the call with one slot, table (0, -1, -1) and
+ * one child.
+ *
+ * check != 0 also checks the rows: xnorm finite (rule 1), w finite and > 0
+ * (rule 2).  The lowest offending row and its rule go to *badRow / *badRule
+ * (-1 / 0 when none; either may be NULL) and the call fails naming it; the
+ * outputs are then undefined.  The call synchronizes the stream to read the
+ * flag.
+ *
+ * cyc_bkm_predict_dev: the tree as HOST int32 arrays of numNodes entries, node
+ * 0 the root: numChildren (0, 1 or 2), firstChild (the children are
+ * firstChild, firstChild + 1; above the node's own index) and leafIndex (>= 0
+ * at a leaf); centers (numNodes x numFeatures, device).  From the root a row
+ * goes to the child of the smaller sqdist(child, x), the first on a tie, down
+ * to a leaf: pred (int32, device) is its leafIndex, cost (fp64, device, may be
+ * NULL) that last sqdist (a tree of one leaf: sqdist(root, x)).  It does not
+ * synchronize.
+ *
+ * workspaceBytes (0: 256 MiB) bounds the summary's chunk partials:
+ * cyc_bkm_chunks_per_launch chunks go through per launch (more launches when
+ * it is smaller, never other bits; at least one chunk).  cyc_bkm_tile_rows
+ * (rows per workgroup of the assign step and the descent) and
+ * cyc_bkm_panel_cols (columns staged in LDS at a time) report the tiling.
+ * fp64 throughout, fixed-order sums, no atomics on doubles: two calls on the
+ * same inputs give the same bits. */
+typedef struct cyc_bkm_plan_s* cyc_bkm_plan;
+
+int cyc_bkm_plan_create(int32_t numFeatures, int64_t workspaceBytes, cyc_bkm_plan* plan);
+int cyc_bkm_plan_destroy(cyc_bkm_plan plan);
+int64_t cyc_bkm_tile_rows(cyc_bkm_plan plan);
+int64_t cyc_bkm_panel_cols(cyc_bkm_plan plan);
+int64_t cyc_bkm_chunk_rows(cyc_bkm_plan plan);
+int64_t cyc_bkm_chunks_per_launch(cyc_bkm_plan plan);
+int64_t cyc_bkm_max_children(cyc_bkm_plan plan);
+int cyc_bkm_step_dev(cyc_bkm_plan plan, const double* X, const double* xnorm, const double* w,
+                     int64_t nrows, const int32_t* slot, int32_t numSlots, const int32_t* table,
+                     int32_t numChildren, const double* centers, const double* cnorm,
+                     int32_t* newSlot, int64_t* count, double* sums, int32_t check,
+                     int64_t* badRow, int32_t* badRule, void* stream);
+int cyc_bkm_predict_dev(cyc_bkm_plan plan, const double* X, int64_t nrows, int32_t numNodes,
+                        const int32_t* firstChild, const int32_t* numChildren,
+                        const int32_t* leafIndex, const double* centers, int32_t* pred,
+                        double* cost, void* stream);
+
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
  * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
