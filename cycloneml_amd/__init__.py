@@ -38,6 +38,13 @@ from .regression import (  # noqa: F401
     WeightedLeastSquares,
     WeightedLeastSquaresModel,
 )
+from .tree import (  # noqa: F401
+    DecisionTreeClassificationModel,
+    DecisionTreeClassifier,
+    DecisionTreeRegressionModel,
+    DecisionTreeRegressor,
+    DTPlan,
+)
 from .regression_summary import (  # noqa: F401
     LinearRegressionSummary,
     LinearRegressionTrainingSummary,

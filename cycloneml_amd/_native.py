@@ -214,6 +214,21 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _i32, _pi64, _pi32, _vp]),
     "cyc_bkm_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp]),
+    "cyc_dt_plan_create": (ctypes.c_int, [_i32, _i32, _i64, ctypes.POINTER(_vp)]),
+    "cyc_dt_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_dt_max_features": (_i64, []),
+    "cyc_dt_max_nodes": (_i64, []),
+    "cyc_dt_run_rows": (_i64, []),
+    "cyc_dt_num_stats": (_i64, [_vp]),
+    "cyc_dt_runs_per_launch": (_i64, [_vp, _i32]),
+    # thresholds, numSplits, the tables and the tree arrays: host pointers
+    "cyc_dt_check_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _pi64, _pi32, _vp]),
+    "cyc_dt_bin_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "cyc_dt_route_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "cyc_dt_histogram_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _i32,
+                                            _vp, _vp]),
+    "cyc_dt_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "cyc_als_segment": (ctypes.c_int, []),
     "cyc_als_side_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp,
                                            ctypes.POINTER(_vp)]),
