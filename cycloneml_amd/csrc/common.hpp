@@ -55,6 +55,7 @@ struct KernelTimer {
 // kCscRowBlock; colptr int64[nblocks F + 1] (block-major, then column),
 // rowidx int32, cvals fp64; each (block, column)'s rows in increasing order.
 constexpr int64_t kCscRowBlock = 1 << 18;
+// rowptr must be zero-based (rowptr[0] == 0): CYC_ERR_INVALID_ARG otherwise.
 int build_csc(const int64_t* rowptr, const int32_t* colidx, const double* vals, int64_t n, int F,
               int64_t rowBlock,
               DeviceBuffer& colptr, DeviceBuffer& rowidx, DeviceBuffer& cvals, hipStream_t st);

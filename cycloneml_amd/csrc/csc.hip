@@ -143,9 +143,18 @@ int check_csr_indices(const int64_t* rowptr, const int32_t* colidx, int64_t n, i
 
 int build_csc(const int64_t* rowptr, const int32_t* colidx, const double* vals, int64_t n, int F,
               int64_t rowBlock, DeviceBuffer& colptr, DeviceBuffer& rowidx, DeviceBuffer& cvals, hipStream_t st) {
-  int64_t nnz = 0;
+  int64_t nnz = 0, base = 0;
+  CYC_HIP(hipMemcpyAsync(&base, rowptr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   CYC_HIP(hipMemcpyAsync(&nnz, rowptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   CYC_HIP(hipStreamSynchronize(st));
+  // k_row_of, the keys and the gathers index colidx / vals at the absolute
+  // rowptr[r] and size their scratch by rowptr[n]: a slice of a larger CSR
+  // (rowptr[0] > 0) would be read past its end
+  if (base != 0) {
+    set_error("requirement failed: rowptr[0] must be 0 for the CSC copy, got " +
+              std::to_string(base) + " (rebase the row pointers of a CSR slice)");
+    return CYC_ERR_INVALID_ARG;
+  }
   const int64_t nb = std::max<int64_t>((n + rowBlock - 1) / rowBlock, 1);
   const int64_t nkeys = nb * F;
   int rc;

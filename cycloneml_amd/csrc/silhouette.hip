@@ -128,6 +128,7 @@ __global__ __launch_bounds__(256) void k_silh_score(const double* __restrict__ X
   __shared__ double rMin[4][SR];
   __shared__ double rOwn[4][SR];
   __shared__ int rHas[4][SR];
+  __shared__ int rOwnHas[4][SR];
   __shared__ double sS[SR], sW[SR];
   const int t = threadIdx.x, r = t & (SR - 1), q = t >> 6;
   const int64_t row0 = (int64_t)blockIdx.x * SR, row = row0 + r;
@@ -140,8 +141,14 @@ __global__ __launch_bounds__(256) void k_silh_score(const double* __restrict__ X
   const double nrm = ok ? xnorm[row] : 1.0;
   const double xsq = dmul(nrm, nrm);
   if (q == 0) sInv[r] = 1.0 / nrm;
-  double best = __builtin_inf(), ownD = 0.0;
-  bool hasBest = false, hasOwn = false;
+  double ownD = 0.0;
+  bool hasOwn = false;
+  // q == 0: the other clusters' minimum so far.  Set.min is a reduceLeft in
+  // cluster-id order and `x <= y` is not associative over NaN (nor blind to
+  // the sign of a zero), so the four quarters of a tile are folded here in
+  // id order, tile after tile, not per thread across tiles.
+  double nb = 0.0;
+  bool hb = false;
   for (int c0 = 0; c0 < k; c0 += SC) {
     double acc[16];
 #pragma unroll
@@ -166,6 +173,10 @@ __global__ __launch_bounds__(256) void k_silh_score(const double* __restrict__ X
         for (int u = 0; u < 16; ++u) acc[u] = dadd(acc[u], dmul(xv, Ys[q * 16 + u][kk]));
       }
     }
+    // this quarter's reduceLeft m; once it has met a NaN it no longer
+    // depends on what came before it (NaN <= y is false)
+    double m = 0.0;
+    bool hasM = false, nanM = false;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int c = c0 + q * 16 + u;
@@ -178,27 +189,33 @@ __global__ __launch_bounds__(256) void k_silh_score(const double* __restrict__ X
         hasOwn = true;
       } else {
         // Scala's Set.min: reduceLeft keeping x when x <= y
-        best = (hasBest && best <= dist) ? best : dist;
-        hasBest = true;
+        m = (hasM && m <= dist) ? m : dist;
+        hasM = true;
+        nanM = nanM || dist != dist;
+      }
+    }
+    // the next write of rMin / rHas is behind the next tile's slice barriers
+    rMin[q][r] = m;
+    rHas[q][r] = (hasM ? 1 : 0) | (nanM ? 2 : 0);
+    __syncthreads();
+    if (q == 0) {
+      for (int qq = 0; qq < 4; ++qq) {
+        if (!(rHas[qq][r] & 1)) continue;
+        const double x = rMin[qq][r];
+        nb = (hb && !(rHas[qq][r] & 2) && nb <= x) ? nb : x;
+        hb = true;
       }
     }
   }
-  rMin[q][r] = best;
   rOwn[q][r] = ownD;
-  rHas[q][r] = (hasOwn ? 1 : 0) | (hasBest ? 2 : 0);
+  rOwnHas[q][r] = hasOwn ? 1 : 0;
   __syncthreads();
   if (q == 0) {
     double s = 0.0, wt = 0.0;
     if (ok) {
-      double nb = 0.0, cur = 0.0;
-      bool hb = false;
-      for (int qq = 0; qq < 4; ++qq) {
-        if (rHas[qq][r] & 1) cur = rOwn[qq][r];
-        if (rHas[qq][r] & 2) {
-          nb = (hb && nb <= rMin[qq][r]) ? nb : rMin[qq][r];
-          hb = true;
-        }
-      }
+      double cur = 0.0;
+      for (int qq = 0; qq < 4; ++qq)
+        if (rOwnHas[qq][r]) cur = rOwn[qq][r];
       wt = w ? w[row] : 1.0;
       const double Wo = W[own];
       if (Wo == wt) {

@@ -524,7 +524,11 @@ typedef struct cyc_logistic_plan_s* cyc_logistic_plan;
  * (row block, column).  Passing it to cyc_binary_logistic_add_csr_dev
  * replaces the gradient's fp64-atomic scatter by per-column sums
  * (deterministic: blocks in order, each block's rows in order).  Costs 12
- * bytes per nonzero + 8 bytes per (row block, column). */
+ * bytes per nonzero + 8 bytes per (row block, column).
+ * rowptr must be zero-based: rowptr[0] == 0 and rowptr[n] == nnz, colidx and
+ * vals holding exactly the n rows.  A slice of a larger CSR whose rowptr
+ * starts above 0 is refused with CYC_ERR_INVALID_ARG (rebase it first); the
+ * SparseVector index checks run before that and name the lowest bad row. */
 typedef struct cyc_csc_s* cyc_csc;
 int cyc_csc_build_dev(const int64_t* rowptr, const int32_t* colidx, const double* vals,
                       int64_t n, int32_t numFeatures, void* stream, cyc_csc* out);
