@@ -45,6 +45,13 @@ from .tree import (  # noqa: F401
     DecisionTreeRegressor,
     DTPlan,
 )
+from .forest import (  # noqa: F401
+    RandomForestClassificationModel,
+    RandomForestClassifier,
+    RandomForestRegressionModel,
+    RandomForestRegressor,
+    RFPlan,
+)
 from .regression_summary import (  # noqa: F401
     LinearRegressionSummary,
     LinearRegressionTrainingSummary,

@@ -229,6 +229,22 @@ SIGNATURES = {
                                             _vp, _vp]),
     "cyc_dt_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_rf_plan_create": (ctypes.c_int, [_i32, _i32, _i64, ctypes.POINTER(_vp)]),
+    "cyc_rf_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_rf_max_trees": (_i64, []),
+    "cyc_rf_max_nodes": (_i64, []),
+    "cyc_rf_run_rows": (_i64, []),
+    "cyc_rf_num_stats": (_i64, [_vp]),
+    "cyc_rf_sub_runs": (_i64, [_i32]),
+    "cyc_rf_runs_per_launch": (_i64, [_vp, _i32, _i32]),
+    # the bag's table, slotStart, the tables, nodeOf, nodeFeat and the trees: host pointers
+    "cyc_rf_bag_dev": (ctypes.c_int, [_vp, _i64, _i32, _i64, ctypes.c_uint64, _vp, _i32, _vp,
+                                      _vp]),
+    "cyc_rf_route_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "cyc_rf_histogram_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp,
+                                            _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "cyc_rf_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "cyc_als_segment": (ctypes.c_int, []),
     "cyc_als_side_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp,
                                            ctypes.POINTER(_vp)]),

@@ -58,7 +58,10 @@
 #include <vector>
 
 #include "common.hpp"
+#include "decision_tree.hpp"
 #include "kmeans_sums.hpp"
+
+using namespace cyc::dt;
 
 enum { DT_RULE_NONE = 0, DT_RULE_FEATURE = 1, DT_RULE_LABEL = 2, DT_RULE_WEIGHT = 3 };
 
@@ -72,33 +75,13 @@ struct cyc_dt_plan_s {
 
 namespace {
 
-constexpr int kMaxBins = 256;               // a bin is a byte
-constexpr int kMaxSplits = kMaxBins - 1;    // thresholds per feature, the padded width
-constexpr int kMaxClasses = 1024;
-constexpr int kMaxFeatures = 65535 * 16;    // gridDim.y of k_dt_bin's panels
+// the bounds shared with random_forest.hip: decision_tree.hpp
 constexpr int kBinPanel = 16;               // features whose thresholds are staged together
 constexpr int kBinRows = 4096;              // rows per k_dt_bin workgroup
-constexpr int kRunRows = 4096;              // rows per run of the histogram
-constexpr int kLanes = 64;                  // features per k_dt_hist workgroup (one wave)
-constexpr int kWindow = 128;                // accumulators per lane: 64 KiB of LDS
-constexpr int kMaxNodes = 4096;             // nodes per histogram call
-constexpr int kMaxTreeNodes = 1 << 24;
-constexpr int64_t kDefaultWorkspace = (int64_t)256 << 20;
 constexpr unsigned long long kNoBad = ~0ull;
-static_assert(kMaxNodes + 1 <= cyc::kmsums::kMaxK, "nodes + the parked cluster are sorted");
-static_assert(kWindow * kLanes * sizeof(double) <= 65536, "the accumulators fit a workgroup's LDS");
-
-inline int num_stats(int C) { return C ? C + 1 : 4; }
 
 __device__ __forceinline__ void dt_flag(unsigned long long* bad, int64_t row, int rule) {
   atomicMin(bad, (unsigned long long)row * 4ull + (unsigned long long)rule);
-}
-
-// the label of a row as a class index, or -1 (never an index)
-__device__ __forceinline__ int dt_label(double y, int C) {
-  if (!(y >= 0.0 && y < (double)C)) return -1;
-  const int c = (int)y;
-  return (double)c == y ? c : -1;
 }
 
 __global__ __launch_bounds__(256) void k_dt_check(const double* __restrict__ X,

@@ -204,24 +204,33 @@ class BestSplits:
 
 
 def best_splits(hist, numSplits, numClasses: int, impurity: str, minInstancesPerNode: int = 1,
-                minWeightPerNode: float = 0.0, minInfoGain: float = 0.0) -> BestSplits:
+                minWeightPerNode: float = 0.0, minInfoGain: float = 0.0,
+                features=None) -> BestSplits:
     """binsToBestSplit over hist (K x d x B x S), features with numSplits[f]
-    splits: the first maximum of the gain in (feature, split) order."""
+    splits: the first maximum of the gain in (feature, split) order.  features
+    (K x m, ascending per node; a forest's per-node subsets): hist is K x m x B x
+    S over each node's own features, the parent's statistics come from the
+    node's first listed feature with splits (its first feature when none has),
+    and the feature returned is the listed one."""
     hist = np.asarray(hist, dtype=np.float64)
     K, d, B, S = hist.shape
     ns = np.asarray(numSplits, dtype=np.int64)
+    if features is not None:
+        features = np.asarray(features, dtype=np.int64).reshape(K, d)
+        ns = ns[features]
+    else:
+        ns = np.broadcast_to(ns, (K, d))
     cum = np.cumsum(hist, axis=2)
-    tot = cum[:, np.arange(d), np.minimum(ns, B - 1), :]            # (K, d, S)
+    tot = np.take_along_axis(cum, np.minimum(ns, B - 1)[:, :, None, None], axis=2)[:, :, 0, :]
     nsp = max(B - 1, 1)
     left = cum[:, :, :nsp, :] if B > 1 else np.zeros((K, d, 1, S))
     right = tot[:, :, None, :] - left
-    exists = np.arange(nsp)[None, :] < ns[:, None]                  # (d, nsp)
-    with_splits = np.nonzero(ns > 0)[0]
-    if with_splits.size:
-        f0 = int(with_splits[0])
-        parent = left[:, f0, 0, :] + right[:, f0, 0, :]
-    else:
-        parent = np.cumsum(hist[:, 0], axis=1)[:, -1, :]
+    exists = np.arange(nsp)[None, None, :] < ns[:, :, None]         # (K, d, nsp)
+    has = ns > 0
+    f0 = np.argmax(has, axis=1)                                     # the first with splits
+    k = np.arange(K)
+    parent = np.where(has.any(axis=1)[:, None], left[k, f0, 0, :] + right[k, f0, 0, :],
+                      np.cumsum(hist[:, 0], axis=1)[:, -1, :])
     imp = calculate(parent, numClasses, impurity)
     lc, rc = stat_count(left, numClasses), stat_count(right, numClasses)
     limp, rimp = calculate(left, numClasses, impurity), calculate(right, numClasses, impurity)
@@ -233,15 +242,14 @@ def best_splits(hist, numSplits, numClasses: int, impurity: str, minInstancesPer
     # this package's rule: a gain that is NaN (both sides without weight) is invalid too
     invalid = invalid | ~(gain >= minInfoGain)
     gain = np.where(invalid, INVALID_GAIN, gain)
-    gain = np.where(exists[None], gain, -np.inf)
+    gain = np.where(exists, gain, -np.inf)
     flat = gain.reshape(K, d * nsp)
     at = np.argmax(flat, axis=1)                                   # the first maximum
     bf, bs = at // nsp, at % nsp
-    k = np.arange(K)
     g = flat[k, at]
     g = np.where(np.isfinite(g), g, INVALID_GAIN)
-    return BestSplits(bf, bs, g, parent, imp, left[k, bf, bs], right[k, bf, bs],
-                      limp[k, bf, bs], rimp[k, bf, bs])
+    return BestSplits(bf if features is None else features[k, bf], bs, g, parent, imp,
+                      left[k, bf, bs], right[k, bf, bs], limp[k, bf, bs], rimp[k, bf, bs])
 
 
 # ------------------------------------------------------------------------ tree
@@ -551,7 +559,7 @@ class DeviceStep:
         n = int(self.X.shape[0])
         sizes = parallel.allgather_object(n)
         rank = parallel.world()[0]
-        lo = int(sum(sizes[:rank]))
+        lo = self.rowOffset = int(sum(sizes[:rank]))     # this rank's first global row
         if rows is None:
             Xs = self.X.cpu().numpy()
             ws = None if self.weights is None else self.weights.cpu().numpy()

@@ -1023,6 +1023,83 @@ int cyc_dt_predict_dev(cyc_dt_plan plan, const double* X, int64_t nrows, int32_t
                        const double* leafRaw, int32_t* leaf, double* pred, double* raw,
                        double* prob, void* stream);
 
+/* --------------------------------------------------------- RandomForest
+ * numTrees bagged trees of ml/tree/impl/RandomForest.scala grown level by level
+ * over ONE binned image (cyc_dt_check_dev / cyc_dt_bin_dev above), every node
+ * over its own subset of numSubset features.  A plan holds numFeatures,
+ * numClasses (0: regression) and the workspace, as a DecisionTree plan does.
+ * numTrees <= cyc_rf_max_trees.
+ *
+ * State (device, tree-major).  bag: numTrees x nrows uint8, the times tree t
+ * drew row r (NULL: every row once).  slot: numTrees x nrows int32, the compact
+ * id of the node row r sits in in tree t, -1: parked.  Per-tree host tables are
+ * concatenated: tree t's entries are slotStart[t] .. slotStart[t + 1] (HOST,
+ * int32, one more entry than trees, slotStart[0] = 0).
+ *
+ * cyc_rf_bag_dev: bag[t][r] = the number of table entries <= u, u = the top 53
+ * bits of mix(seed, 0, t, rowOffset + r); table (HOST, tableLen <= 255 uint64
+ * <= 2^53, ascending) holds floor(cdf_k 2^53).  mix(seed, stream, tree, index) =
+ * fin(fin(fin(seed + G) + G (2 tree + stream + 1)) + G (index + 1)) mod 2^64,
+ * fin = splitmix64's finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >>
+ * 27, z *= 0x94D049BB133111EB, z ^= z >> 31), G = 0x9E3779B97F4A7C15.
+ *
+ * cyc_rf_route_dev: cyc_dt_route_dev's rule for every (tree, row) in one launch,
+ * table (HOST, 4 slotStart[numTrees] int32) addressed through slotStart.
+ *
+ * cyc_rf_histogram_dev: one call covers the nodes 0 .. numNodes - 1 (<=
+ * cyc_rf_max_nodes) of the trees [tree0, tree1), (tree1 - tree0) nrows <= 2^31 -
+ * 1.  bag and slot are the WHOLE arrays (tree 0's first); slotStart (tree1 -
+ * tree0 + 1 entries) and nodeOf (slotStart's last entry many, node or -1 per
+ * slot) belong to the range; a node may be named by slots of one tree only.
+ * nodeFeat (HOST, numNodes x numSubset int32 in [0, numFeatures); NULL: numSubset
+ * = numFeatures, every feature in order) lists each node's features.  hist
+ * (device, numNodes x numSubset x numBins x cyc_rf_num_stats) is SET to the sums
+ * over each node's pairs at [j][image[row][nodeFeat[node][j]]]: classification
+ * stat[label] += count w and stat[numClasses] += count, regression iw = count w:
+ * iw, iw y, (iw y) y, count, count = bag[t][row].  A pair whose slot sits out or
+ * whose count is 0 is never loaded.  A node's pairs are cut in row order into
+ * runs of cyc_rf_run_rows and every run into cyc_rf_sub_runs(numSubset) fixed
+ * slices; the partials are folded in (run, slice) order.  workspaceBytes holds
+ * cyc_rf_runs_per_launch runs' partials: a smaller one means more launches,
+ * never other bits, and neither do the tree range or the grouping of nodes.
+ *
+ * cyc_rf_predict_dev: the trees as concatenated HOST arrays in
+ * cyc_dt_predict_dev's form, tree t's nodes at nodeStart[t] .. nodeStart[t + 1]
+ * with firstChild and leafIndex local to the tree, its leaves at leafStart[t] ..;
+ * leafValue (HOST, fp64): per leaf numClasses votes (class weights over their
+ * sum; zeros for a leaf without weight) or the regression prediction.  Outputs
+ * (device, each may be NULL): leaf (nrows x numTrees int32, the tree's own leaf
+ * index), raw (nrows x numClasses, the votes added in tree order), prob (raw over
+ * its sum taken in class order, raw itself when the sum is 0), pred (the first
+ * largest raw; regression: the predictions added in tree order over numTrees).
+ * A classifier's prob and pred need raw.  It does not synchronize. */
+typedef struct cyc_rf_plan_s* cyc_rf_plan;
+
+int cyc_rf_plan_create(int32_t numFeatures, int32_t numClasses, int64_t workspaceBytes,
+                       cyc_rf_plan* plan);
+int cyc_rf_plan_destroy(cyc_rf_plan plan);
+int64_t cyc_rf_max_trees(void);
+int64_t cyc_rf_max_nodes(void);
+int64_t cyc_rf_run_rows(void);
+int64_t cyc_rf_num_stats(cyc_rf_plan plan);
+int64_t cyc_rf_sub_runs(int32_t numSubset);
+int64_t cyc_rf_runs_per_launch(cyc_rf_plan plan, int32_t numSubset, int32_t numBins);
+int cyc_rf_bag_dev(cyc_rf_plan plan, int64_t nrows, int32_t numTrees, int64_t rowOffset,
+                   uint64_t seed, const uint64_t* table, int32_t tableLen, uint8_t* bag,
+                   void* stream);
+int cyc_rf_route_dev(cyc_rf_plan plan, const uint8_t* image, int64_t nrows, int32_t numTrees,
+                     int32_t* slot, const int32_t* slotStart, const int32_t* table, void* stream);
+int cyc_rf_histogram_dev(cyc_rf_plan plan, const uint8_t* image, const double* y, const double* w,
+                         const uint8_t* bag, int64_t nrows, const int32_t* slot, int32_t tree0,
+                         int32_t tree1, const int32_t* slotStart, const int32_t* nodeOf,
+                         int32_t numNodes, int32_t numSubset, const int32_t* nodeFeat,
+                         int32_t numBins, double* hist, void* stream);
+int cyc_rf_predict_dev(cyc_rf_plan plan, const double* X, int64_t nrows, int32_t numTrees,
+                       const int32_t* nodeStart, const int32_t* leafStart, const int32_t* feature,
+                       const double* threshold, const int32_t* firstChild,
+                       const int32_t* leafIndex, const double* leafValue, int32_t* leaf,
+                       double* raw, double* prob, double* pred, void* stream);
+
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
  * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
