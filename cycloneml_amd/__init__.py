@@ -52,6 +52,13 @@ from .forest import (  # noqa: F401
     RandomForestRegressor,
     RFPlan,
 )
+from .gbt import (  # noqa: F401
+    GBTClassificationModel,
+    GBTClassifier,
+    GBTPlan,
+    GBTRegressionModel,
+    GBTRegressor,
+)
 from .regression_summary import (  # noqa: F401
     LinearRegressionSummary,
     LinearRegressionTrainingSummary,

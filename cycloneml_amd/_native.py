@@ -245,6 +245,15 @@ SIGNATURES = {
                                             _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "cyc_rf_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_gbt_plan_create": (ctypes.c_int, [_i32, ctypes.POINTER(_vp)]),
+    "cyc_gbt_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_gbt_lds_nodes": (_i64, []),
+    "cyc_gbt_max_trees": (_i64, []),
+    # the tree arrays and treeWeights: host pointers
+    "cyc_gbt_update_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                          _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_gbt_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cyc_als_segment": (ctypes.c_int, []),
     "cyc_als_side_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp,
                                            ctypes.POINTER(_vp)]),

@@ -15,7 +15,10 @@ every node's split among its m features, and one route per level moves the rows
 of all trees.  A row adds numSamples w to its label's statistic (numSamples w,
 (numSamples w) y, ((numSamples w) y) y for the variance) and numSamples to the
 raw count, which minInstancesPerNode tests; minWeightFractionPerNode multiplies
-the un-bagged sum of the weights.
+the un-bagged sum of the weights.  grow_forest is prepare_step (the rows'
+checks, the totals, the thresholds and the image, once per fit) followed by
+grow_prepared (the bag and the level loop); a boosted fit (gbt.py) prepares
+once and grows a forest of one tree per iteration on the step's current labels.
 
 The step object adds to tree.py's: bag(numTrees, table, seed), histogram(t0,
 t1, slotStart, nodeOf, K, B, nodeFeat, m) over the trees [t0, t1) and
@@ -201,16 +204,39 @@ def grow_forest(step, d: int, numClasses: int, impurity: str, numTrees: int,
     T.check_params(maxDepth, maxBins, minInstancesPerNode, minWeightFractionPerNode, minInfoGain,
                    impurity, bool(numClasses))
     check_forest_params(numTrees, subsamplingRate)
-    m, nt = int(numFeaturesPerNode), int(numTrees)
+    m = int(numFeaturesPerNode)
     _require(1 <= m <= d, f"numFeaturesPerNode must be in [1, {d}] but got {m}")
+    thresholds, _, wsum = prepare_step(step, maxBins, seed)
+    roots = grow_prepared(step, d, numClasses, impurity, numTrees, m, thresholds, wsum, maxDepth,
+                          minInstancesPerNode, minWeightFractionPerNode, minInfoGain, bootstrap,
+                          subsamplingRate, seed, pruneTree, nodesPerCall)
+    return roots, thresholds
+
+
+def prepare_step(step, maxBins: int, seed: int):
+    """What a fit does once with its rows: the rows' checks, the totals, the
+    split candidates from the sample and the binned image.  (thresholds, n, the
+    un-bagged sum of the weights)."""
     step.check()
     n, wsum = step.totals()
     _require(n > 0, "DecisionTree requires size of input RDD > 0, but was given by empty one.")
     thresholds = T.all_splits(*step.sample(T.sample_rows(maxBins, n, seed)), maxBins, n, wsum)
+    step.bin(thresholds)
+    return thresholds, n, wsum
+
+
+def grow_prepared(step, d: int, numClasses: int, impurity: str, numTrees: int,
+                  numFeaturesPerNode: int, thresholds, wsum: float, maxDepth: int = 5,
+                  minInstancesPerNode: int = 1, minWeightFractionPerNode: float = 0.0,
+                  minInfoGain: float = 0.0, bootstrap: bool = True, subsamplingRate: float = 1.0,
+                  seed: int = 0, pruneTree: bool = True, nodesPerCall=None):
+    """The bag and the level loop over a step that prepare_step has binned (a
+    boosted fit grows many forests of one tree over one image, each on the
+    step's current labels): the roots in tree order."""
+    m, nt = int(numFeaturesPerNode), int(numTrees)
     numSplits = np.array([len(t) for t in thresholds], dtype=np.int64)
     B = int(numSplits.max()) + 1
     S = T.num_stats(numClasses)
-    step.bin(thresholds)
     step.bag(nt, bag_table(bootstrap, subsamplingRate), seed)
     minWeight = float(minWeightFractionPerNode) * wsum
     per_call = int(nodesPerCall) if nodesPerCall else \
@@ -262,7 +288,7 @@ def grow_forest(step, d: int, numClasses: int, impurity: str, numTrees: int,
         live = nxt
         level += 1
     roots = [nodes[t][1] for t in range(nt)]
-    return [T.prune(r) if pruneTree else r for r in roots], thresholds
+    return [T.prune(r) if pruneTree else r for r in roots]
 
 
 # ----------------------------------------------------------------------- steps

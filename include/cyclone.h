@@ -1100,6 +1100,61 @@ int cyc_rf_predict_dev(cyc_rf_plan plan, const double* X, int64_t nrows, int32_t
                        const int32_t* leafIndex, const double* leafValue, int32_t* leaf,
                        double* raw, double* prob, double* pred, void* stream);
 
+/* ------------------------------------------------- GradientBoostedTrees
+ * What ml/tree/impl/GradientBoostedTrees.scala's boost does between two trees,
+ * and the descent of a boosted ensemble.  The trees are grown by the
+ * RandomForest entry points above (one tree per iteration on the current
+ * residuals); the loop and the models are host code (cycloneml_amd/gbt.py).  A
+ * plan holds numFeatures and the scratch of the calls.
+ *
+ * cyc_gbt_update_dev: one tree as HOST arrays of numNodes entries in
+ * cyc_dt_predict_dev's breadth-first form (feature, firstChild; -1 at a leaf)
+ * with value[i] the prediction of leaf node i.  The rows come EITHER as the
+ * binned image (uint8, nrows x numFeatures; X NULL) with splitBin[i] the split
+ * of internal node i as a bin (0 .. 254; the position of its threshold among
+ * the feature's thresholds): image byte <= splitBin goes to firstChild, the
+ * byte compared unsigned; OR as fp64 rows X (image NULL) with threshold[i]:
+ * x[feature] <= threshold goes to firstChild.  Per row, every operation rounded
+ * once and unfused: F = pred + value treeWeight, pred (device, in/out) <- F,
+ *   loss 0 squared   g = -2 (y - F),                    e = (y - F)(y - F)
+ *   loss 1 absolute  g = y - F < 0 ? 1 : -1,             e = |y - F|
+ *   loss 2 logistic  g = (-4 y) / (1 + exp((2 y) F)),    e = 2 log1pExp(-(2 y) F)
+ * resid (device, may be NULL) <- -g, and sums (device, 2 doubles) is SET to the
+ * sum of e w and the sum of w (w NULL: every weight 1.0).  The sums have one
+ * fixed order: 256 consecutive rows through a binary tree (stride 128 .. 1),
+ * the workgroups' partials t, t + 256, .. added in order by thread t of one
+ * workgroup and those 256 through the same tree.  A tree of at most
+ * cyc_gbt_lds_nodes nodes is staged in LDS, a larger one is read from global
+ * memory; the bits do not depend on it.  Two calls give the same bytes.
+ *
+ * cyc_gbt_predict_dev: numTrees (<= cyc_gbt_max_trees) trees as concatenated
+ * HOST arrays, tree t's nodes at nodeStart[t] .. nodeStart[t + 1], firstChild
+ * local to the tree, leafIndex and value per NODE (read at leaves), treeWeights
+ * (HOST, numTrees).  margin = sum over t of value_t treeWeights[t], from 0.0 in
+ * tree order, each product rounded before its add, whatever the tiling of the
+ * trees in LDS.  Outputs (device, each may be NULL): leaf (nrows x numTrees
+ * int32), margin, raw = (-margin, margin), prob = (1 - p, p) with p = 1 / (1 +
+ * exp(-2 margin)), pred (classifier != 0: margin > 0 ? 1 : 0, else margin); raw
+ * and prob need classifier != 0.  Both calls upload the tree from the plan's
+ * own host copy and wait for that upload; they do not wait for the kernels. */
+typedef struct cyc_gbt_plan_s* cyc_gbt_plan;
+
+int cyc_gbt_plan_create(int32_t numFeatures, cyc_gbt_plan* plan);
+int cyc_gbt_plan_destroy(cyc_gbt_plan plan);
+int64_t cyc_gbt_lds_nodes(void);
+int64_t cyc_gbt_max_trees(void);
+int cyc_gbt_update_dev(cyc_gbt_plan plan, const uint8_t* image, const double* X, int64_t nrows,
+                       int32_t numNodes, const int32_t* feature, const int32_t* splitBin,
+                       const double* threshold, const int32_t* firstChild, const double* value,
+                       double treeWeight, int32_t loss, const double* y, const double* w,
+                       double* pred, double* resid, double* sums, void* stream);
+int cyc_gbt_predict_dev(cyc_gbt_plan plan, const double* X, int64_t nrows, int32_t numTrees,
+                        const int32_t* nodeStart, const int32_t* feature,
+                        const double* threshold, const int32_t* firstChild,
+                        const int32_t* leafIndex, const double* value, const double* treeWeights,
+                        int32_t classifier, int32_t* leaf, double* margin, double* raw,
+                        double* prob, double* pred, void* stream);
+
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
  * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
