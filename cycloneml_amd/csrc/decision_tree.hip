@@ -25,8 +25,8 @@
 //   k_dt_key      the node (0 .. K - 1) a row's slot maps to in this call, K
 //                 for every other row: the key of kmeans_sums.hpp's stable
 //                 sort_clusters (cluster K is skipped).
-//   k_dt_runs     runStart: a node's rows, in row order, are cut into runs of
-//                 kRunRows rows.
+//   k_dt_runs     runStart: a node's rows (the forest's pairs), in row order,
+//                 are cut into runs of kRunRows.
 //   k_dt_hist     a workgroup is one wave: one run x kLanes features x one
 //                 window of kWindow accumulators.  A lane owns a feature; its
 //                 accumulators acc[slot][lane] sit in LDS (a double per lane per
@@ -37,8 +37,11 @@
 //                 The run's rows are gathered through the permutation in row
 //                 order, d contiguous bytes each, 8 rows' loads in flight.  The
 //                 window goes to the workspace as part[run][flat][feature].
-//   k_dt_fold     per node, the runs in order onto the histogram (zero at the
-//                 start of the call), written as node x feature x bin x stat.
+//   k_dt_fold     per node, the partials in (run, sub-run) order onto the
+//                 histogram (zero at the start of the call), written as node x
+//                 feature x bin x stat.  The tree's run leaves one partial (Q =
+//                 1) over all d features, the forest's Q over its m subset
+//                 features; an empty sub-run adds +0.0, which changes no bit.
 //                 The workspace holds a group of runs: a smaller one means more
 //                 launches of the pair and the same chain, so the same bits.
 //   k_dt_predict  a thread per row walks the tree (x[f] <= threshold goes to
@@ -47,6 +50,11 @@
 //                 probability.
 // No atomics on doubles, every sum has one fixed order: two calls on the same
 // inputs give the same bits.
+//
+// random_forest.hip and gbt.hip share what decision_tree.hpp declares: the
+// checks of a plan, of a route table and of a tree a kernel may walk, and the
+// driver of a histogram call (histogram_runs: sort, k_dt_runs, then per group of
+// runs the caller's hist kernel and k_dt_fold) are defined here once.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -69,13 +77,13 @@ struct cyc_dt_plan_s {
   std::mutex mu;
   int d = 0, C = 0;   // C = 0: variance
   int64_t wsBytes = 0;
-  cyc::kmsums::SortScratch sort;
-  cyc::DeviceBuffer table, key, ws, bad, runStart, thr, cnt, tree, leaf;
+  HistScratch hist;
+  cyc::DeviceBuffer table, bad, thr, cnt, tree, leaf;
 };
 
 namespace {
 
-// the bounds shared with random_forest.hip: decision_tree.hpp
+// the bounds and rules shared with random_forest.hip and gbt.hip: decision_tree.hpp
 constexpr int kBinPanel = 16;               // features whose thresholds are staged together
 constexpr int kBinRows = 4096;              // rows per k_dt_bin workgroup
 constexpr unsigned long long kNoBad = ~0ull;
@@ -139,11 +147,7 @@ __global__ __launch_bounds__(256) void k_dt_route(const uint8_t* __restrict__ im
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
   const int s = slot[r];
-  int out = -1;
-  if ((unsigned)s < (unsigned)numSlots) {
-    const int f = table[4 * s];
-    if (f >= 0) out = (int)image[r * d + f] <= table[4 * s + 1] ? table[4 * s + 2] : table[4 * s + 3];
-  }
+  const int out = route_slot(s, numSlots, table, image + r * d);
   if (out != s) slot[r] = out;
 }
 
@@ -153,13 +157,7 @@ __global__ __launch_bounds__(256) void k_dt_key(const int32_t* __restrict__ slot
                                                 int K, int32_t* __restrict__ key) {
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
-  const int s = slot ? slot[r] : 0;
-  int k = K;
-  if ((unsigned)s < (unsigned)numSlots) {
-    const int c = nodeOf[s];
-    if ((unsigned)c < (unsigned)K) k = c;
-  }
-  key[r] = k;
+  key[r] = node_of_slot(slot ? slot[r] : 0, numSlots, nodeOf, K);
 }
 
 __global__ void k_dt_runs(const int64_t* __restrict__ cstart, int K, int64_t* __restrict__ runStart) {
@@ -180,22 +178,17 @@ __global__ __launch_bounds__(kLanes) void k_dt_hist(
     const double* __restrict__ w, const int32_t* __restrict__ perm,
     const int64_t* __restrict__ cstart, const int64_t* __restrict__ runStart, int K, int64_t g0,
     int B, int C, double* __restrict__ part) {
-  __shared__ double acc[kWindow][kLanes];
+  __shared__ double acc[kWindow * kLanes];
   const int64_t run = g0 + blockIdx.x;
   if (run >= runStart[K]) return;
-  int lo = 0, hi = K;   // the node: the last c with runStart[c] <= run
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (runStart[mid] <= run) lo = mid; else hi = mid;
-  }
-  const int c = lo;
-  const int64_t first = cstart[c] + (run - runStart[c]) * kRunRows;
-  const int cnt = (int)(min<int64_t>(cstart[c + 1], first + kRunRows) - first);
+  int c, cnt;
+  int64_t first;
+  locate_run(run, runStart, cstart, K, c, first, cnt);
   const int lane = threadIdx.x, f = blockIdx.y * kLanes + lane;
   const int S = C ? C + 1 : 4, flats = S * B;
   const int a0 = blockIdx.z * kWindow;
 #pragma unroll 8
-  for (int a = 0; a < kWindow; ++a) acc[a][lane] = 0.0;
+  for (int a = 0; a < kWindow; ++a) acc[a * kLanes + lane] = 0.0;
   if (f < d) {
     for (int p0 = 0; p0 < cnt; p0 += 8) {
       int bin[8];
@@ -212,42 +205,30 @@ __global__ __launch_bounds__(kLanes) void k_dt_hist(
       for (int u = 0; u < 8; ++u) {
         // a byte outside the bins is never an index
         if (p0 + u >= cnt || bin[u] >= B) continue;
-        if (C) {
-          const int lb = dt_label(yv[u], C);
-          const int a = lb * B + bin[u] - a0, b = C * B + bin[u] - a0;
-          if (lb >= 0 && (unsigned)a < (unsigned)kWindow) acc[a][lane] = dadd(acc[a][lane], wv[u]);
-          if ((unsigned)b < (unsigned)kWindow) acc[b][lane] = dadd(acc[b][lane], 1.0);
-        } else {
-          const double wy = dmul(wv[u], yv[u]);
-          const double v[4] = {wv[u], wy, dmul(wy, yv[u]), 1.0};
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            const int a = s * B + bin[u] - a0;
-            if ((unsigned)a < (unsigned)kWindow) acc[a][lane] = dadd(acc[a][lane], v[s]);
-          }
-        }
+        add_row(acc, lane, bin[u], yv[u], wv[u], 1.0, a0, kWindow, B, C);
       }
     }
     double* out = part + (int64_t)blockIdx.x * flats * d;
-    for (int a = 0; a < kWindow && a0 + a < flats; ++a) out[(int64_t)(a0 + a) * d + f] = acc[a][lane];
+    for (int a = 0; a < kWindow && a0 + a < flats; ++a) out[(int64_t)(a0 + a) * d + f] = acc[a * kLanes + lane];
   }
 }
 
-// hist[c] (d x B x S) += node c's runs of the group [g0, g0 + group), in order
+// hist[c] (m x B x S) += node c's partials of the runs [g0, g0 + group), Q per
+// run, in (run, sub-run) order
 __global__ __launch_bounds__(256) void k_dt_fold(const double* __restrict__ part,
-                                                 const int64_t* __restrict__ runStart, int d,
-                                                 int B, int S, int64_t g0, int64_t group,
+                                                 const int64_t* __restrict__ runStart, int m,
+                                                 int B, int S, int Q, int64_t g0, int64_t group,
                                                  double* __restrict__ hist) {
   const int c = blockIdx.x;
-  const int64_t len = (int64_t)S * B * d;
+  const int64_t len = (int64_t)S * B * m;
   const int64_t a = max<int64_t>(runStart[c], g0), b = min<int64_t>(runStart[c + 1], g0 + group);
   if (a >= b) return;
   for (int64_t e = (int64_t)blockIdx.y * 256 + threadIdx.x; e < len; e += (int64_t)gridDim.y * 256) {
-    const int f = (int)(e % d), flat = (int)(e / d);
+    const int jf = (int)(e % m), flat = (int)(e / m);
     const int s = flat / B, bin = flat % B;
-    double* dst = hist + (int64_t)c * len + ((int64_t)f * B + bin) * S + s;
+    double* dst = hist + (int64_t)c * len + ((int64_t)jf * B + bin) * S + s;
     double v = *dst;
-    for (int64_t run = a; run < b; ++run) v = dadd(v, part[(run - g0) * len + e]);
+    for (int64_t sr = (a - g0) * Q; sr < (b - g0) * Q; ++sr) v = dadd(v, part[sr * len + e]);
     *dst = v;
   }
 }
@@ -292,29 +273,119 @@ int reset_bad(cyc_dt_plan_s* p, hipStream_t st) {
   return CYC_OK;
 }
 
-int64_t runs_per_launch(const cyc_dt_plan_s* p, int B) {
-  return std::max<int64_t>(1, p->wsBytes / (8 * (int64_t)num_stats(p->C) * B * p->d));
+}  // namespace
+
+// ------------------------------------------- shared host pieces (decision_tree.hpp)
+namespace cyc {
+namespace dt {
+
+int check_features(const char* name, int32_t numFeatures) {
+  CYC_REQUIRE(numFeatures >= 1 && numFeatures <= kMaxFeatures,
+              std::string(name) + " supports 1 to " + std::to_string(kMaxFeatures) +
+                  " features but got " + std::to_string(numFeatures));
+  return CYC_OK;
 }
 
-}  // namespace
+int probe_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    cyc::set_error("no HIP device visible");
+    return CYC_ERR_NO_DEVICE;
+  }
+  return CYC_OK;
+}
+
+int check_plan(const char* name, int32_t numFeatures, int32_t numClasses, int64_t workspaceBytes) {
+  if (int rc = check_features(name, numFeatures)) return rc;
+  CYC_REQUIRE(numClasses >= 0 && numClasses <= kMaxClasses,
+              std::string(name) + " supports 1 to " + std::to_string(kMaxClasses) +
+                  " classes (0: regression) but got " + std::to_string(numClasses));
+  CYC_REQUIRE(workspaceBytes >= 0, "workspaceBytes must not be negative");
+  return probe_device();
+}
+
+int check_route_table(const int32_t* table, int numEntries, int d, const char* what) {
+  for (int s = 0; s < numEntries; ++s) {
+    const int32_t f = table[4 * s], b = table[4 * s + 1];
+    if (f < 0) continue;
+    const auto at = [&] { return std::string(what) + " " + std::to_string(s); };
+    CYC_REQUIRE(f < d && b >= 0 && b < kMaxSplits,
+                at() + " must split a feature in [0, " + std::to_string(d) + ") at a bin in [0, " +
+                    std::to_string(kMaxSplits) + ")");
+    CYC_REQUIRE(table[4 * s + 2] >= -1 && table[4 * s + 3] >= -1,
+                "the new slots of " + at() + " must be -1 or a slot");
+  }
+  return CYC_OK;
+}
+
+int check_tree(int64_t nn, const int32_t* feature, const int32_t* firstChild,
+               const int32_t* splitBin, const int32_t* leafIndex, int64_t numLeaves, int d,
+               const std::string& ofTree) {
+  for (int64_t i = 0; i < nn; ++i) {
+    const int32_t fc = firstChild[i];
+    const auto node = [&] { return "node " + std::to_string(i) + ofTree; };
+    if (fc >= 0) {
+      CYC_REQUIRE(fc > i && (int64_t)fc + 2 <= nn,
+                  "the children of " + node() + " must follow it and lie inside the tree");
+      CYC_REQUIRE(feature[i] >= 0 && feature[i] < d,
+                  node() + " must split a feature in [0, " + std::to_string(d) + ")");
+      CYC_REQUIRE(!splitBin || (splitBin[i] >= 0 && splitBin[i] < kMaxSplits),
+                  node() + " must split at a bin in [0, " + std::to_string(kMaxSplits) + ")");
+    } else {
+      CYC_REQUIRE(!leafIndex || (leafIndex[i] >= 0 && leafIndex[i] < numLeaves),
+                  "leaf " + node() + " needs a leaf index in [0, " + std::to_string(numLeaves) +
+                      ")");
+    }
+  }
+  return CYC_OK;
+}
+
+int histogram_runs(HistScratch& scratch, int64_t pairs, int K, int m, int Q, int B, int C,
+                   int64_t wsBytes, double* hist, hipStream_t st, const HistLabels& labels,
+                   const HistLaunch& launchHist) {
+  if (int rc = scratch.runStart.reserve(sizeof(int64_t) * (size_t)(K + 1))) return rc;
+  int64_t maxChunks = 0;
+  // d = 0: the sort's own chunk buffers are not used here
+  if (int rc = cyc::kmsums::sort_clusters(scratch.sort, (int32_t*)scratch.key.ptr, pairs, 0, K + 1,
+                                          st, maxChunks))
+    return rc;
+  const int32_t* perm = (const int32_t*)scratch.sort.perm.ptr;
+  const int64_t* cstart = (const int64_t*)scratch.sort.cstart.ptr;
+  int64_t* runStart = (int64_t*)scratch.runStart.ptr;
+  hipLaunchKernelGGL(k_dt_runs, dim3(1), dim3(64), 0, st, cstart, K, runStart);
+  CYC_LAUNCH_CHECK(labels.runs);
+  // the run count is on the device: the bound is launched, the surplus leaves
+  const int S = num_stats(C);
+  const int64_t len = (int64_t)S * B * m;
+  const int64_t maxRuns = pairs / kRunRows + K;
+  const int64_t group = std::min(maxRuns, runs_per_launch(wsBytes, C, m, Q, B));
+  if (int rc = scratch.ws.reserve(sizeof(double) * (size_t)(group * Q * len))) return rc;
+  const unsigned foldBlocks = (unsigned)std::min<int64_t>((len + 255) / 256, 1024);
+  for (int64_t g0 = 0; g0 < maxRuns; g0 += group) {
+    const int64_t gc = std::min(group, maxRuns - g0);
+    {
+      cyc::KernelTimer timer(labels.hist, st);
+      launchHist(g0, gc, perm, cstart, runStart);
+      CYC_LAUNCH_CHECK(labels.hist);
+    }
+    cyc::KernelTimer timer(labels.fold, st);
+    hipLaunchKernelGGL(k_dt_fold, dim3((unsigned)K, foldBlocks), dim3(256), 0, st,
+                       (const double*)scratch.ws.ptr, (const int64_t*)runStart, m, B, S, Q, g0, gc,
+                       hist);
+    CYC_LAUNCH_CHECK(labels.fold);
+  }
+  return CYC_OK;
+}
+
+}  // namespace dt
+}  // namespace cyc
 
 extern "C" {
 
 int cyc_dt_plan_create(int32_t numFeatures, int32_t numClasses, int64_t workspaceBytes,
                        cyc_dt_plan* plan) {
   CYC_REQUIRE(plan != nullptr, "plan must not be null");
-  CYC_REQUIRE(numFeatures >= 1 && numFeatures <= kMaxFeatures,
-              "DecisionTree supports 1 to " + std::to_string(kMaxFeatures) +
-                  " features but got " + std::to_string(numFeatures));
-  CYC_REQUIRE(numClasses >= 0 && numClasses <= kMaxClasses,
-              "DecisionTree supports 1 to " + std::to_string(kMaxClasses) +
-                  " classes (0: regression) but got " + std::to_string(numClasses));
-  CYC_REQUIRE(workspaceBytes >= 0, "workspaceBytes must not be negative");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    cyc::set_error("no HIP device visible");
-    return CYC_ERR_NO_DEVICE;
-  }
+  if (int rc = check_plan("DecisionTree", numFeatures, numClasses, workspaceBytes)) return rc;
   auto* p = new cyc_dt_plan_s();
   p->d = numFeatures;
   p->C = numClasses;
@@ -333,7 +404,9 @@ int64_t cyc_dt_max_nodes(void) { return kMaxNodes; }
 int64_t cyc_dt_run_rows(void) { return kRunRows; }
 int64_t cyc_dt_num_stats(cyc_dt_plan plan) { return plan ? num_stats(plan->C) : -1; }
 int64_t cyc_dt_runs_per_launch(cyc_dt_plan plan, int32_t numBins) {
-  return plan && numBins >= 1 && numBins <= kMaxBins ? runs_per_launch(plan, numBins) : -1;
+  return plan && numBins >= 1 && numBins <= kMaxBins
+             ? runs_per_launch(plan->wsBytes, plan->C, plan->d, 1, numBins)
+             : -1;
 }
 
 int cyc_dt_check_dev(cyc_dt_plan plan, const double* X, const double* y, const double* w,
@@ -421,16 +494,7 @@ int cyc_dt_route_dev(cyc_dt_plan plan, const uint8_t* image, int64_t nrows, int3
   CYC_REQUIRE(nrows >= 0 && nrows <= INT32_MAX, "0 <= nrows <= 2147483647");
   CYC_REQUIRE(numSlots >= 1 && table != nullptr, "a table of at least one slot");
   cyc_dt_plan_s* p = plan;
-  for (int s = 0; s < numSlots; ++s) {
-    const int32_t f = table[4 * s], b = table[4 * s + 1];
-    if (f < 0) continue;
-    CYC_REQUIRE(f < p->d && b >= 0 && b < kMaxSplits,
-                "slot " + std::to_string(s) + " must split a feature in [0, " +
-                    std::to_string(p->d) + ") at a bin in [0, " + std::to_string(kMaxSplits) +
-                    ")");
-    CYC_REQUIRE(table[4 * s + 2] >= -1 && table[4 * s + 3] >= -1,
-                "the new slots of slot " + std::to_string(s) + " must be -1 or a slot");
-  }
+  if (int rc = check_route_table(table, numSlots, p->d, "slot")) return rc;
   if (nrows == 0) return CYC_OK;
   CYC_REQUIRE(image != nullptr && slot != nullptr, "non-null image and slot");
   hipStream_t st = cyc::as_stream(stream);
@@ -472,45 +536,23 @@ int cyc_dt_histogram_dev(cyc_dt_plan plan, const uint8_t* image, const double* y
   if (int rc = p->table.reserve(sizeof(int32_t) * (size_t)numSlots)) return rc;
   CYC_HIP(hipMemcpyAsync(p->table.ptr, nodeOf, sizeof(int32_t) * (size_t)numSlots,
                          hipMemcpyHostToDevice, st));
-  if (int rc = p->key.reserve(sizeof(int32_t) * (size_t)nrows)) return rc;
-  if (int rc = p->runStart.reserve(sizeof(int64_t) * (size_t)(K + 1))) return rc;
-  int32_t* key = (int32_t*)p->key.ptr;
+  if (int rc = p->hist.key.reserve(sizeof(int32_t) * (size_t)nrows)) return rc;
   {
     cyc::KernelTimer timer("k_dt_key", st);
     hipLaunchKernelGGL(k_dt_key, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, slot,
-                       nrows, numSlots, (const int32_t*)p->table.ptr, K, key);
+                       nrows, numSlots, (const int32_t*)p->table.ptr, K, (int32_t*)p->hist.key.ptr);
     CYC_LAUNCH_CHECK("k_dt_key");
   }
-  int64_t maxChunks = 0;
-  // d = 0: the sort's own chunk buffers are not used here
-  if (int rc = cyc::kmsums::sort_clusters(p->sort, key, nrows, 0, K + 1, st, maxChunks)) return rc;
-  const int32_t* perm = (const int32_t*)p->sort.perm.ptr;
-  const int64_t* cstart = (const int64_t*)p->sort.cstart.ptr;
-  int64_t* runStart = (int64_t*)p->runStart.ptr;
-  hipLaunchKernelGGL(k_dt_runs, dim3(1), dim3(64), 0, st, cstart, K, runStart);
-  CYC_LAUNCH_CHECK("k_dt_runs");
-  // the run count is on the device: the bound is launched, the surplus leaves
-  const int64_t maxRuns = nrows / kRunRows + K;
-  const int64_t group = std::min(maxRuns, runs_per_launch(p, B));
-  if (int rc = p->ws.reserve(sizeof(double) * (size_t)(group * len))) return rc;
   const unsigned panels = (unsigned)((d + kLanes - 1) / kLanes);
   const unsigned passes = (unsigned)((S * B + kWindow - 1) / kWindow);
-  const unsigned foldBlocks = (unsigned)std::min<int64_t>((len + 255) / 256, 1024);
-  for (int64_t g0 = 0; g0 < maxRuns; g0 += group) {
-    const int64_t gc = std::min(group, maxRuns - g0);
-    {
-      cyc::KernelTimer timer("k_dt_hist", st);
-      hipLaunchKernelGGL(k_dt_hist, dim3((unsigned)gc, panels, passes), dim3(kLanes), 0, st, image,
-                         d, y, w, perm, cstart, (const int64_t*)runStart, K, g0, B, p->C,
-                         (double*)p->ws.ptr);
-      CYC_LAUNCH_CHECK("k_dt_hist");
-    }
-    cyc::KernelTimer timer("k_dt_fold", st);
-    hipLaunchKernelGGL(k_dt_fold, dim3((unsigned)K, foldBlocks), dim3(256), 0, st,
-                       (const double*)p->ws.ptr, (const int64_t*)runStart, d, B, S, g0, gc, hist);
-    CYC_LAUNCH_CHECK("k_dt_fold");
-  }
-  return CYC_OK;
+  // a run leaves one partial over all d features: Q = 1, m = d
+  return histogram_runs(
+      p->hist, nrows, K, d, 1, B, p->C, p->wsBytes, hist, st, {"k_dt_runs", "k_dt_hist", "k_dt_fold"},
+      [&](int64_t g0, int64_t gc, const int32_t* perm, const int64_t* cstart,
+          const int64_t* runStart) {
+        hipLaunchKernelGGL(k_dt_hist, dim3((unsigned)gc, panels, passes), dim3(kLanes), 0, st, image,
+                           d, y, w, perm, cstart, runStart, K, g0, B, p->C, (double*)p->hist.ws.ptr);
+      });
 }
 
 int cyc_dt_predict_dev(cyc_dt_plan plan, const double* X, int64_t nrows, int32_t numNodes,
@@ -528,21 +570,8 @@ int cyc_dt_predict_dev(cyc_dt_plan plan, const double* X, int64_t nrows, int32_t
               "non-null node arrays");
   cyc_dt_plan_s* p = plan;
   CYC_REQUIRE(numLeaves >= 1 && numLeaves <= numNodes, "1 to numNodes leaves");
-  for (int i = 0; i < numNodes; ++i) {
-    const int32_t fc = firstChild[i];
-    if (fc >= 0) {
-      CYC_REQUIRE(fc > i && (int64_t)fc + 2 <= numNodes,
-                  "the children of node " + std::to_string(i) +
-                      " must follow it and lie inside the tree");
-      CYC_REQUIRE(feature[i] >= 0 && feature[i] < p->d,
-                  "node " + std::to_string(i) + " must split a feature in [0, " +
-                      std::to_string(p->d) + ")");
-    } else {
-      CYC_REQUIRE(leafIndex[i] >= 0 && leafIndex[i] < numLeaves,
-                  "leaf node " + std::to_string(i) + " needs a leaf index in [0, " +
-                      std::to_string(numLeaves) + ")");
-    }
-  }
+  if (int rc = check_tree(numNodes, feature, firstChild, nullptr, leafIndex, numLeaves, p->d, ""))
+    return rc;
   CYC_REQUIRE((raw == nullptr && prob == nullptr) || (p->C > 0 && leafRaw != nullptr),
               "raw and prob need a classifier's plan and leafRaw");
   CYC_REQUIRE(pred == nullptr || leafPred != nullptr, "pred needs leafPred");

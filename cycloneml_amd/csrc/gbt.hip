@@ -232,25 +232,6 @@ __global__ __launch_bounds__(kBlock) void k_gbt_predict(
   if (pred) pred[r] = classifier ? (sum > 0.0 ? 1.0 : 0.0) : sum;
 }
 
-// the checks every tree array gets before a kernel may walk it; nn nodes at `at`
-int check_tree(int tree, int64_t nn, const int32_t* feature, const int32_t* firstChild,
-               const int32_t* splitBin, int d) {
-  for (int64_t i = 0; i < nn; ++i) {
-    const int32_t fc = firstChild[i];
-    if (fc < 0) continue;
-    CYC_REQUIRE(fc > i && (int64_t)fc + 2 <= nn,
-                "the children of node " + std::to_string(i) + " of tree " + std::to_string(tree) +
-                    " must follow it and lie inside the tree");
-    CYC_REQUIRE(feature[i] >= 0 && feature[i] < d,
-                "node " + std::to_string(i) + " of tree " + std::to_string(tree) +
-                    " must split a feature in [0, " + std::to_string(d) + ")");
-    CYC_REQUIRE(!splitBin || (splitBin[i] >= 0 && splitBin[i] < kMaxSplits),
-                "node " + std::to_string(i) + " of tree " + std::to_string(tree) +
-                    " must split at a bin in [0, " + std::to_string(kMaxSplits) + ")");
-  }
-  return CYC_OK;
-}
-
 }  // namespace
 
 struct cyc_gbt_plan_s {
@@ -265,14 +246,8 @@ extern "C" {
 
 int cyc_gbt_plan_create(int32_t numFeatures, cyc_gbt_plan* plan) {
   CYC_REQUIRE(plan != nullptr, "plan must not be null");
-  CYC_REQUIRE(numFeatures >= 1 && numFeatures <= kMaxFeatures,
-              "GBT supports 1 to " + std::to_string(kMaxFeatures) + " features but got " +
-                  std::to_string(numFeatures));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    cyc::set_error("no HIP device visible");
-    return CYC_ERR_NO_DEVICE;
-  }
+  if (int rc = check_features("GBT", numFeatures)) return rc;
+  if (int rc = probe_device()) return rc;
   auto* p = new cyc_gbt_plan_s();
   p->d = numFeatures;
   *plan = p;
@@ -309,7 +284,8 @@ int cyc_gbt_update_dev(cyc_gbt_plan plan, const uint8_t* image, const double* X,
   CYC_REQUIRE(asImage ? splitBin != nullptr : threshold != nullptr,
               "image rows need splitBin, fp64 rows need threshold");
   CYC_REQUIRE(sums != nullptr, "sums must not be null");
-  if (int rc = check_tree(0, numNodes, feature, firstChild, asImage ? splitBin : nullptr, p->d))
+  if (int rc = check_tree(numNodes, feature, firstChild, asImage ? splitBin : nullptr, nullptr, 0,
+                          p->d, " of tree 0"))
     return rc;
   hipStream_t st = cyc::as_stream(stream);
   if (nrows == 0) {
@@ -383,7 +359,9 @@ int cyc_gbt_predict_dev(cyc_gbt_plan plan, const double* X, int64_t nrows, int32
                 "tree " + std::to_string(t) + " needs 1 to " + std::to_string(kMaxTreeNodes) +
                     " nodes");
     const int64_t at = nodeStart[t];
-    if (int rc = check_tree(t, nn, feature + at, firstChild + at, nullptr, p->d)) return rc;
+    if (int rc = check_tree(nn, feature + at, firstChild + at, nullptr, nullptr, 0, p->d,
+                            " of tree " + std::to_string(t)))
+      return rc;
   }
   if (nrows == 0) return CYC_OK;
   CYC_REQUIRE(X != nullptr, "rows must not be null");

@@ -53,10 +53,11 @@
 //                 leaves at d = 64.  The row is perm - (t - t0) n with the tree
 //                 known per node; per row the gather is image[r d + f], y[r], w[r]
 //                 and bag[t][r].
-//   k_rf_fold     per node, the partials in (run, sub-run) order onto hist (K x m
-//                 x B x S), zero at the start of the call.  An empty sub-run adds
-//                 +0.0, which changes no bit.  A smaller workspace means more
-//                 launches and the same chain.
+//   the runs and the fold are decision_tree.hip's k_dt_runs and k_dt_fold,
+//                 launched by its histogram_runs (timed here as k_rf_runs and
+//                 k_rf_fold): per node, the partials in (run, sub-run) order onto
+//                 hist (K x m x B x S), zero at the start of the call.  A smaller
+//                 workspace means more launches and the same chain.
 //   k_rf_predict  a thread per row walks every tree in order (the trees
 //                 concatenated breadth first, flatten_tree's form, with per-tree
 //                 node and leaf offsets), writes the leaf matrix and adds the
@@ -88,8 +89,8 @@ struct cyc_rf_plan_s {
   std::mutex mu;
   int d = 0, C = 0;   // C = 0: variance
   int64_t wsBytes = 0;
-  cyc::kmsums::SortScratch sort;
-  cyc::DeviceBuffer meta, key, ws, runStart, bagTable, tree, thr, leaf;
+  HistScratch hist;
+  cyc::DeviceBuffer meta, bagTable, tree, thr, leaf;
   std::vector<int32_t> nodeTree;   // the tree of every node of the last histogram call
 };
 
@@ -142,12 +143,7 @@ __global__ __launch_bounds__(256) void k_rf_route(const uint8_t* __restrict__ im
   const int s0 = slotStart[t], numSlots = slotStart[t + 1] - s0;
   const int64_t at = (int64_t)t * n + r;
   const int s = slot[at];
-  int out = -1;
-  if ((unsigned)s < (unsigned)numSlots) {
-    const int32_t* e = table + 4 * (int64_t)(s0 + s);
-    const int f = e[0];
-    if (f >= 0) out = (int)image[r * d + f] <= e[1] ? e[2] : e[3];
-  }
+  const int out = route_slot(s, numSlots, table + 4 * (int64_t)s0, image + r * d);
   if (out != s) slot[at] = out;
 }
 
@@ -164,22 +160,8 @@ __global__ __launch_bounds__(256) void k_rf_key(const int32_t* __restrict__ slot
   const int64_t pair = (int64_t)tl * n + r;
   const int s0 = slotStart[tl], numSlots = slotStart[tl + 1] - s0;
   const int s = slot ? slot[pair] : 0;
-  int k = K;
-  if ((unsigned)s < (unsigned)numSlots && (!bag || bag[pair] != 0)) {
-    const int c = nodeOf[s0 + s];
-    if ((unsigned)c < (unsigned)K) k = c;
-  }
-  key[pair] = k;
-}
-
-__global__ void k_rf_runs(const int64_t* __restrict__ cstart, int K, int64_t* __restrict__ runStart) {
-  if (blockIdx.x || threadIdx.x) return;
-  int64_t s = 0;
-  for (int c = 0; c < K; ++c) {
-    runStart[c] = s;
-    s += (cstart[c + 1] - cstart[c] + kRunRows - 1) / kRunRows;
-  }
-  runStart[K] = s;
+  // a row drawn 0 times sits out as the skip slot does
+  key[pair] = node_of_slot(!bag || bag[pair] != 0 ? s : -1, numSlots, nodeOf + s0, K);
 }
 
 // Run g0 + blockIdx.x, subset features blockIdx.y P .. (lane % P), sub-run lane /
@@ -196,14 +178,9 @@ __global__ __launch_bounds__(kLanes) void k_rf_hist(
   extern __shared__ double acc[];   // [W][kLanes]
   const int64_t run = g0 + blockIdx.x;
   if (run >= runStart[K]) return;
-  int lo = 0, hi = K;   // the node: the last c with runStart[c] <= run
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (runStart[mid] <= run) lo = mid; else hi = mid;
-  }
-  const int c = lo;
-  const int64_t first = cstart[c] + (run - runStart[c]) * kRunRows;
-  const int cnt = (int)(min<int64_t>(cstart[c + 1], first + kRunRows) - first);
+  int c, cnt;
+  int64_t first;
+  locate_run(run, runStart, cstart, K, c, first, cnt);
   const int lane = threadIdx.x, Q = kLanes / P, sub = (kRunRows + Q - 1) / Q;
   const int q = lane / P, jf = blockIdx.y * P + lane % P;
   const int S = C ? C + 1 : 4, flats = S * B;
@@ -232,46 +209,11 @@ __global__ __launch_bounds__(kLanes) void k_rf_hist(
       // a byte outside the bins is never an index
       if (p0 + u >= p1 || bin[u] >= B) continue;
       const double cntv = (double)ns[u];
-      const double iw = dmul(cntv, wv[u]);
-      if (C) {
-        const int lb = dt_label(yv[u], C);
-        const int a = lb * B + bin[u] - a0, b = C * B + bin[u] - a0;
-        if (lb >= 0 && (unsigned)a < (unsigned)W)
-          acc[a * kLanes + lane] = dadd(acc[a * kLanes + lane], iw);
-        if ((unsigned)b < (unsigned)W) acc[b * kLanes + lane] = dadd(acc[b * kLanes + lane], cntv);
-      } else {
-        const double wy = dmul(iw, yv[u]);
-        const double v[4] = {iw, wy, dmul(wy, yv[u]), cntv};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int a = s * B + bin[u] - a0;
-          if ((unsigned)a < (unsigned)W) acc[a * kLanes + lane] = dadd(acc[a * kLanes + lane], v[s]);
-        }
-      }
+      add_row(acc, lane, bin[u], yv[u], dmul(cntv, wv[u]), cntv, a0, W, B, C);
     }
   }
   double* out = part + ((int64_t)blockIdx.x * Q + q) * flats * m;
   for (int a = 0; a < W && a0 + a < flats; ++a) out[(int64_t)(a0 + a) * m + jf] = acc[a * kLanes + lane];
-}
-
-// hist[c] (m x B x S) += node c's partials of the runs [g0, g0 + group), in (run,
-// sub-run) order
-__global__ __launch_bounds__(256) void k_rf_fold(const double* __restrict__ part,
-                                                 const int64_t* __restrict__ runStart, int m,
-                                                 int B, int S, int Q, int64_t g0, int64_t group,
-                                                 double* __restrict__ hist) {
-  const int c = blockIdx.x;
-  const int64_t len = (int64_t)S * B * m;
-  const int64_t a = max<int64_t>(runStart[c], g0), b = min<int64_t>(runStart[c + 1], g0 + group);
-  if (a >= b) return;
-  for (int64_t e = (int64_t)blockIdx.y * 256 + threadIdx.x; e < len; e += (int64_t)gridDim.y * 256) {
-    const int jf = (int)(e % m), flat = (int)(e / m);
-    const int s = flat / B, bin = flat % B;
-    double* dst = hist + (int64_t)c * len + ((int64_t)jf * B + bin) * S + s;
-    double v = *dst;
-    for (int64_t sr = (a - g0) * Q; sr < (b - g0) * Q; ++sr) v = dadd(v, part[sr * len + e]);
-    *dst = v;
-  }
 }
 
 // nodes (int32): [feature | firstChild | leafIndex], total nodes each, a tree's
@@ -335,11 +277,6 @@ __global__ __launch_bounds__(256) void k_rf_predict(
   }
 }
 
-int64_t runs_per_launch(const cyc_rf_plan_s* p, int m, int B) {
-  const int Q = kLanes / panel_width(m);
-  return std::max<int64_t>(1, p->wsBytes / (8 * (int64_t)num_stats(p->C) * B * m * Q));
-}
-
 }  // namespace
 
 extern "C" {
@@ -347,18 +284,7 @@ extern "C" {
 int cyc_rf_plan_create(int32_t numFeatures, int32_t numClasses, int64_t workspaceBytes,
                        cyc_rf_plan* plan) {
   CYC_REQUIRE(plan != nullptr, "plan must not be null");
-  CYC_REQUIRE(numFeatures >= 1 && numFeatures <= kMaxFeatures,
-              "RandomForest supports 1 to " + std::to_string(kMaxFeatures) +
-                  " features but got " + std::to_string(numFeatures));
-  CYC_REQUIRE(numClasses >= 0 && numClasses <= kMaxClasses,
-              "RandomForest supports 1 to " + std::to_string(kMaxClasses) +
-                  " classes (0: regression) but got " + std::to_string(numClasses));
-  CYC_REQUIRE(workspaceBytes >= 0, "workspaceBytes must not be negative");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    cyc::set_error("no HIP device visible");
-    return CYC_ERR_NO_DEVICE;
-  }
+  if (int rc = check_plan("RandomForest", numFeatures, numClasses, workspaceBytes)) return rc;
   auto* p = new cyc_rf_plan_s();
   p->d = numFeatures;
   p->C = numClasses;
@@ -381,7 +307,8 @@ int64_t cyc_rf_sub_runs(int32_t numSubset) {
 }
 int64_t cyc_rf_runs_per_launch(cyc_rf_plan plan, int32_t numSubset, int32_t numBins) {
   return plan && numSubset >= 1 && numSubset <= plan->d && numBins >= 1 && numBins <= kMaxBins
-             ? runs_per_launch(plan, numSubset, numBins)
+             ? runs_per_launch(plan->wsBytes, plan->C, numSubset,
+                               kLanes / panel_width(numSubset), numBins)
              : -1;
 }
 
@@ -427,16 +354,7 @@ int cyc_rf_route_dev(cyc_rf_plan plan, const uint8_t* image, int64_t nrows, int3
   cyc_rf_plan_s* p = plan;
   const int total = slotStart[numTrees];
   CYC_REQUIRE(total >= 1, "a table of at least one slot");
-  for (int s = 0; s < total; ++s) {
-    const int32_t f = table[4 * s], b = table[4 * s + 1];
-    if (f < 0) continue;
-    CYC_REQUIRE(f < p->d && b >= 0 && b < kMaxSplits,
-                "slot entry " + std::to_string(s) + " must split a feature in [0, " +
-                    std::to_string(p->d) + ") at a bin in [0, " + std::to_string(kMaxSplits) +
-                    ")");
-    CYC_REQUIRE(table[4 * s + 2] >= -1 && table[4 * s + 3] >= -1,
-                "the new slots of slot entry " + std::to_string(s) + " must be -1 or a slot");
-  }
+  if (int rc = check_route_table(table, total, p->d, "slot entry")) return rc;
   if (nrows == 0) return CYC_OK;
   CYC_REQUIRE(image != nullptr && slot != nullptr, "non-null image and slot");
   hipStream_t st = cyc::as_stream(stream);
@@ -525,53 +443,31 @@ int cyc_rf_histogram_dev(cyc_rf_plan plan, const uint8_t* image, const double* y
   if (nodeFeat)
     CYC_HIP(hipMemcpyAsync(md + nSS + nNO + nNT, nodeFeat, sizeof(int32_t) * nNF,
                            hipMemcpyHostToDevice, st));
-  if (int rc = p->key.reserve(sizeof(int32_t) * (size_t)pairs)) return rc;
-  if (int rc = p->runStart.reserve(sizeof(int64_t) * (size_t)(K + 1))) return rc;
-  int32_t* key = (int32_t*)p->key.ptr;
+  if (int rc = p->hist.key.reserve(sizeof(int32_t) * (size_t)pairs)) return rc;
   const int64_t off = (int64_t)tree0 * nrows;
   const uint8_t* bag0 = bag ? bag + off : nullptr;
   {
     cyc::KernelTimer timer("k_rf_key", st);
     hipLaunchKernelGGL(k_rf_key, dim3((unsigned)((nrows + 255) / 256), (unsigned)TR), dim3(256), 0,
                        st, slot ? slot + off : nullptr, bag0, nrows, (const int32_t*)md,
-                       (const int32_t*)(md + nSS), K, key);
+                       (const int32_t*)(md + nSS), K, (int32_t*)p->hist.key.ptr);
     CYC_LAUNCH_CHECK("k_rf_key");
   }
-  int64_t maxChunks = 0;
-  // d = 0: the sort's own chunk buffers are not used here
-  if (int rc = cyc::kmsums::sort_clusters(p->sort, key, pairs, 0, K + 1, st, maxChunks)) return rc;
-  const int32_t* perm = (const int32_t*)p->sort.perm.ptr;
-  const int64_t* cstart = (const int64_t*)p->sort.cstart.ptr;
-  int64_t* runStart = (int64_t*)p->runStart.ptr;
-  hipLaunchKernelGGL(k_rf_runs, dim3(1), dim3(64), 0, st, cstart, K, runStart);
-  CYC_LAUNCH_CHECK("k_rf_runs");
-  // the run count is on the device: the bound is launched, the surplus leaves
   const int P = panel_width(m), Q = kLanes / P;
-  const int64_t maxRuns = pairs / kRunRows + K;
-  const int64_t group = std::min(maxRuns, runs_per_launch(p, m, B));
-  if (int rc = p->ws.reserve(sizeof(double) * (size_t)(group * Q * len))) return rc;
   const int W = std::min(S * B, kWindow);
   const unsigned panels = (unsigned)((m + P - 1) / P);
   const unsigned passes = (unsigned)((S * B + kWindow - 1) / kWindow);
-  const unsigned foldBlocks = (unsigned)std::min<int64_t>((len + 255) / 256, 1024);
-  for (int64_t g0 = 0; g0 < maxRuns; g0 += group) {
-    const int64_t gc = std::min(group, maxRuns - g0);
-    {
-      cyc::KernelTimer timer("k_rf_hist", st);
-      hipLaunchKernelGGL(k_rf_hist, dim3((unsigned)gc, panels, passes), dim3(kLanes),
-                         sizeof(double) * (size_t)W * kLanes, st, image, nrows, d, y, w, bag0, perm,
-                         cstart, (const int64_t*)runStart, K, g0, B, p->C, m, P, W,
-                         (const int32_t*)(md + nSS + nNO),
-                         nodeFeat ? (const int32_t*)(md + nSS + nNO + nNT) : nullptr,
-                         (double*)p->ws.ptr);
-      CYC_LAUNCH_CHECK("k_rf_hist");
-    }
-    cyc::KernelTimer timer("k_rf_fold", st);
-    hipLaunchKernelGGL(k_rf_fold, dim3((unsigned)K, foldBlocks), dim3(256), 0, st,
-                       (const double*)p->ws.ptr, (const int64_t*)runStart, m, B, S, Q, g0, gc, hist);
-    CYC_LAUNCH_CHECK("k_rf_fold");
-  }
-  return CYC_OK;
+  return histogram_runs(
+      p->hist, pairs, K, m, Q, B, p->C, p->wsBytes, hist, st, {"k_rf_runs", "k_rf_hist", "k_rf_fold"},
+      [&](int64_t g0, int64_t gc, const int32_t* perm, const int64_t* cstart,
+          const int64_t* runStart) {
+        hipLaunchKernelGGL(k_rf_hist, dim3((unsigned)gc, panels, passes), dim3(kLanes),
+                           sizeof(double) * (size_t)W * kLanes, st, image, nrows, d, y, w, bag0, perm,
+                           cstart, runStart, K, g0, B, p->C, m, P, W,
+                           (const int32_t*)(md + nSS + nNO),
+                           nodeFeat ? (const int32_t*)(md + nSS + nNO + nNT) : nullptr,
+                           (double*)p->hist.ws.ptr);
+      });
 }
 
 int cyc_rf_predict_dev(cyc_rf_plan plan, const double* X, int64_t nrows, int32_t numTrees,
@@ -596,22 +492,10 @@ int cyc_rf_predict_dev(cyc_rf_plan plan, const double* X, int64_t nrows, int32_t
                 "tree " + std::to_string(t) + " needs 1 to " + std::to_string(kMaxTreeNodes) +
                     " nodes and 1 to as many leaves");
     CYC_REQUIRE(nodeStart[t + 1] > nodeStart[t], "nodeStart must increase");
-    for (int64_t i = 0; i < nn; ++i) {
-      const int64_t at = nodeStart[t] + i;
-      const int32_t fc = firstChild[at];
-      if (fc >= 0) {
-        CYC_REQUIRE(fc > i && (int64_t)fc + 2 <= nn,
-                    "the children of node " + std::to_string(i) + " of tree " + std::to_string(t) +
-                        " must follow it and lie inside the tree");
-        CYC_REQUIRE(feature[at] >= 0 && feature[at] < p->d,
-                    "node " + std::to_string(i) + " of tree " + std::to_string(t) +
-                        " must split a feature in [0, " + std::to_string(p->d) + ")");
-      } else {
-        CYC_REQUIRE(leafIndex[at] >= 0 && leafIndex[at] < nl,
-                    "leaf node " + std::to_string(i) + " of tree " + std::to_string(t) +
-                        " needs a leaf index in [0, " + std::to_string(nl) + ")");
-      }
-    }
+    const int64_t at = nodeStart[t];
+    if (int rc = check_tree(nn, feature + at, firstChild + at, nullptr, leafIndex + at, nl, p->d,
+                            " of tree " + std::to_string(t)))
+      return rc;
   }
   CYC_REQUIRE(prob == nullptr || p->C > 0, "prob needs a classifier's plan");
   CYC_REQUIRE(raw == nullptr || p->C > 0, "raw needs a classifier's plan");

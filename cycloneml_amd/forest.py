@@ -15,18 +15,17 @@ every node's split among its m features, and one route per level moves the rows
 of all trees.  A row adds numSamples w to its label's statistic (numSamples w,
 (numSamples w) y, ((numSamples w) y) y for the variance) and numSamples to the
 raw count, which minInstancesPerNode tests; minWeightFractionPerNode multiplies
-the un-bagged sum of the weights.  grow_forest is prepare_step (the rows'
-checks, the totals, the thresholds and the image, once per fit) followed by
-grow_prepared (the bag and the level loop); a boosted fit (gbt.py) prepares
-once and grows a forest of one tree per iteration on the step's current labels.
+the un-bagged sum of the weights.  The loop itself is tree.py's (prepare_step:
+the rows' checks, the totals, the thresholds and the image, once per fit; then
+grow_prepared: the bag and the level loop); this module's grow_prepared hands it
+the bag's table and the feature subsets.  A boosted fit (gbt.py) prepares once
+and grows a forest of one tree per iteration on the step's current labels.
 
-The step object adds to tree.py's: bag(numTrees, table, seed), histogram(t0,
-t1, slotStart, nodeOf, K, B, nodeFeat, m) over the trees [t0, t1) and
-route(slotStart, table) over all trees.  Per-tree tables are concatenated:
-tree t's slots are the entries slotStart[t] .. slotStart[t + 1].
-ForestDeviceStep (the kernels; histograms go through parallel.allreduce_ once
-per call, so every rank calls fit) and ForestNumpyStep (host rows) are
-interchangeable.
+The step protocol is tree.py's.  ForestDeviceStep runs it on this module's
+kernels for any number of trees, a bag and per-node subsets (histograms go
+through parallel.allreduce_ once per call, so every rank calls fit);
+ForestNumpyStep adds the drawn bag and the rank's row offset to tree.py's
+NumpyStep.  The two are interchangeable.
 
 This project's own rules (Spark's commons-math Poisson sampler and its
 stack-ordered reservoir sampling are not restated, so a fit does not reproduce a
@@ -190,9 +189,8 @@ def check_forest_params(numTrees, subsamplingRate):
              f"subsamplingRate must be in (0, 1] but got {subsamplingRate}.")
 
 
-# ------------------------------------------------------------------ level loop
-def forest_nodes_per_call(m: int, B: int, S: int, maxNodes: int = T.MAX_NODES) -> int:
-    return int(min(maxNodes, T.MAX_NODES, max(1, T.HIST_BYTES // (8 * m * B * S))))
+# ------------------------------------------- level loop (tree.py's, bag and subsets)
+prepare_step = T.prepare_step
 
 
 def grow_forest(step, d: int, numClasses: int, impurity: str, numTrees: int,
@@ -213,82 +211,21 @@ def grow_forest(step, d: int, numClasses: int, impurity: str, numTrees: int,
     return roots, thresholds
 
 
-def prepare_step(step, maxBins: int, seed: int):
-    """What a fit does once with its rows: the rows' checks, the totals, the
-    split candidates from the sample and the binned image.  (thresholds, n, the
-    un-bagged sum of the weights)."""
-    step.check()
-    n, wsum = step.totals()
-    _require(n > 0, "DecisionTree requires size of input RDD > 0, but was given by empty one.")
-    thresholds = T.all_splits(*step.sample(T.sample_rows(maxBins, n, seed)), maxBins, n, wsum)
-    step.bin(thresholds)
-    return thresholds, n, wsum
-
-
 def grow_prepared(step, d: int, numClasses: int, impurity: str, numTrees: int,
                   numFeaturesPerNode: int, thresholds, wsum: float, maxDepth: int = 5,
                   minInstancesPerNode: int = 1, minWeightFractionPerNode: float = 0.0,
                   minInfoGain: float = 0.0, bootstrap: bool = True, subsamplingRate: float = 1.0,
                   seed: int = 0, pruneTree: bool = True, nodesPerCall=None):
-    """The bag and the level loop over a step that prepare_step has binned (a
-    boosted fit grows many forests of one tree over one image, each on the
-    step's current labels): the roots in tree order."""
-    m, nt = int(numFeaturesPerNode), int(numTrees)
-    numSplits = np.array([len(t) for t in thresholds], dtype=np.int64)
-    B = int(numSplits.max()) + 1
-    S = T.num_stats(numClasses)
-    step.bag(nt, bag_table(bootstrap, subsamplingRate), seed)
-    minWeight = float(minWeightFractionPerNode) * wsum
-    per_call = int(nodesPerCall) if nodesPerCall else \
-        forest_nodes_per_call(m, B, S, getattr(step, "maxNodes", T.MAX_NODES))
-    nodes = [{} for _ in range(nt)]
-    live = [{1: 0} for _ in range(nt)]      # per tree: the nodes to split at this level -> slot
-    level = 0
-    while any(live):
-        slotStart = np.zeros(nt + 1, dtype=np.int32)
-        slotStart[1:] = np.cumsum([len(lv) for lv in live])
-        table = np.full((int(slotStart[nt]), 4), -1, dtype=np.int32)
-        order = [(t, i) for t in range(nt) for i in sorted(live[t])]
-        nxt = [{} for _ in range(nt)]
-        for g0 in range(0, len(order), per_call):
-            group = order[g0:g0 + per_call]
-            t0, t1 = group[0][0], group[-1][0] + 1
-            ss = (slotStart[t0:t1 + 1] - slotStart[t0]).astype(np.int32)
-            nodeOf = np.full(int(ss[-1]), -1, dtype=np.int32)
-            for j, (t, i) in enumerate(group):
-                nodeOf[ss[t - t0] + live[t][i]] = j
-            feats = None if m == d else \
-                np.stack([feature_subset(seed, t, i, d, m) for t, i in group])
-            hist = step.histogram(t0, t1, ss, nodeOf, len(group), B, feats, m)
-            best = T.best_splits(hist, numSplits, numClasses, impurity, minInstancesPerNode,
-                                 minWeight, minInfoGain, features=feats)
-            for j, (t, i) in enumerate(group):
-                if i not in nodes[t]:   # the root: its statistics are the first evaluation's
-                    nodes[t][i] = T.Node(best.parent[j], best.impurity[j], numClasses)
-                node = nodes[t][i]
-                gain = float(best.gain[j])
-                if gain <= 0.0 or level == maxDepth:
-                    continue
-                f, s = int(best.feature[j]), int(best.split[j])
-                node.gain = gain
-                node.split = (f, float(thresholds[f][s]))
-                node.left = T.Node(best.left[j], best.leftImp[j], numClasses)
-                node.right = T.Node(best.right[j], best.rightImp[j], numClasses)
-                nodes[t][2 * i], nodes[t][2 * i + 1] = node.left, node.right
-                new = []
-                for child, idx in ((node.left, 2 * i), (node.right, 2 * i + 1)):
-                    if level + 1 == maxDepth or abs(child.impurity) < T.EPSILON:
-                        new.append(-1)
-                    else:
-                        nxt[t][idx] = len(nxt[t])
-                        new.append(nxt[t][idx])
-                table[slotStart[t] + live[t][i]] = (f, s, new[0], new[1])
-        if any(nxt):
-            step.route(slotStart, table)
-        live = nxt
-        level += 1
-    roots = [nodes[t][1] for t in range(nt)]
-    return [T.prune(r) if pruneTree else r for r in roots]
+    """tree.py's level loop with this module's bag and feature subsets, over a
+    step that prepare_step has binned (a boosted fit grows many forests of one
+    tree over one image, each on the step's current labels): the roots in tree
+    order."""
+    m = int(numFeaturesPerNode)
+    subsetOf = None if m == d else (lambda t, i: feature_subset(seed, t, i, d, m))
+    return T.grow_prepared(step, d, numClasses, impurity, numTrees, m, thresholds, wsum, maxDepth,
+                           minInstancesPerNode, minWeightFractionPerNode, minInfoGain,
+                           bag_table(bootstrap, subsamplingRate), subsetOf, seed, pruneTree,
+                           nodesPerCall)
 
 
 # ----------------------------------------------------------------------- steps
@@ -324,16 +261,6 @@ class RFPlan:
     def runs_per_launch(self, numSubset: int, numBins: int) -> int:
         return int(self._lib.cyc_rf_runs_per_launch(self.handle, int(numSubset), int(numBins)))
 
-    def _image(self, image):
-        import torch
-        if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 \
-                or image.dim() != 2 or int(image.shape[1]) != self.numFeatures \
-                or not image.is_contiguous():
-            raise N.IllegalArgumentException(
-                f"requirement failed: the image must be contiguous uint8 (n x {self.numFeatures}) "
-                "on the device")
-        return int(image.shape[0])
-
     @staticmethod
     def _matrix(v, rows, n, dtype, what):
         import torch
@@ -356,7 +283,7 @@ class RFPlan:
 
     def route(self, image, slot, slotStart, table):
         import torch
-        n = self._image(image)
+        n = T.check_image(image, self.numFeatures)
         slotStart = np.ascontiguousarray(slotStart, dtype=np.int32).ravel()
         nt = int(slotStart.size) - 1
         self._matrix(slot, nt, n, torch.int32, "slot")
@@ -373,7 +300,7 @@ class RFPlan:
                        numSubset, nodeFeat, numBins):
         """One cyc_rf_histogram_dev call: (numNodes x numSubset x numBins x numStats)."""
         import torch
-        n = self._image(image)
+        n = T.check_image(image, self.numFeatures)
         T.DTPlan._vector(y, n, torch.float64, "labels")
         if weights is not None:
             T.DTPlan._vector(weights, n, torch.float64, "weights")
@@ -466,16 +393,14 @@ class ForestDeviceStep(DeviceStep):
         super().__init__(X, y, weights, numClasses, workspaceBytes, checked=checked)
         self.rf = RFPlan(self.d, numClasses, workspaceBytes)
         self.maxNodes = self.rf.maxNodes
-        self.slot = self.bagCounts = self.rowOffset = None
-        self.numTrees = 0
+        self.bagCounts = self.rowOffset = None
 
     def bag(self, numTrees: int, table, seed: int):
         import torch
         n = int(self.X.shape[0])
         # the rank's first global row is kept by sample(), from its allgather of the sizes
         _require(self.rowOffset is not None, "bag() follows sample(), which finds the row offset")
-        self.numTrees = int(numTrees)
-        self.slot = torch.zeros((self.numTrees, n), dtype=torch.int32, device=self.X.device)
+        self.slot = torch.zeros((int(numTrees), n), dtype=torch.int32, device=self.X.device)
         self.bagCounts = None if table is None else \
             self.rf.bag(n, numTrees, table, seed, self.rowOffset, self.X.device)
 
@@ -497,60 +422,11 @@ class ForestNumpyStep(NumpyStep):
     def __init__(self, X, y, weights=None, numClasses: int = 0, rowOffset: int = 0):
         super().__init__(X, y, weights, numClasses)
         self.rowOffset = int(rowOffset)
-        self.slot = self.bagCounts = None
-        self.numTrees = 0
 
     def bag(self, numTrees: int, table, seed: int):
-        n = int(self.X.shape[0])
-        self.numTrees = int(numTrees)
-        self.slot = np.zeros((self.numTrees, n), dtype=np.int32)
+        super().bag(numTrees, None, seed)
         self.bagCounts = None if table is None else \
-            bag_counts(seed, numTrees, n, table, self.rowOffset)
-
-    def histogram(self, t0, t1, slotStart, nodeOf, K, B, nodeFeat, m):
-        nodeOf = np.asarray(nodeOf, dtype=np.int64)
-        ss = np.asarray(slotStart, dtype=np.int64)
-        C = self.numClasses
-        S = T.num_stats(C)
-        feats = np.broadcast_to(np.arange(self.d), (K, self.d)) if nodeFeat is None else \
-            np.asarray(nodeFeat, dtype=np.int64).reshape(K, m)
-        hist = np.zeros((K, m, B, S), dtype=np.float64)
-        for t in range(t0, t1):
-            slot = self.slot[t]
-            rows = np.nonzero((slot >= 0) & (slot < ss[t - t0 + 1] - ss[t - t0]))[0]
-            node = nodeOf[ss[t - t0] + slot[rows]]
-            keep = node >= 0
-            if self.bagCounts is not None:
-                keep &= self.bagCounts[t, rows] > 0     # a row drawn 0 times is not loaded
-            rows, node = rows[keep], node[keep]
-            cnt = np.ones(rows.size) if self.bagCounts is None else \
-                self.bagCounts[t, rows].astype(np.float64)
-            iw = cnt * (np.ones(rows.size) if self.weights is None else self.weights[rows])
-            y = self.y[rows]
-            if C:
-                vals = [(y.astype(np.int64), iw), (np.full(rows.size, C), cnt)]
-            else:
-                wy = iw * y
-                vals = [(np.full(rows.size, s), v) for s, v in enumerate((iw, wy, wy * y, cnt))]
-            for j in range(m):
-                b = self.image[rows, feats[node, j]].astype(np.int64)
-                for s, v in vals:
-                    np.add.at(hist, (node, j, b, s), v)      # unbuffered: row order
-        return hist
-
-    def route(self, slotStart, table):
-        table = np.asarray(table, dtype=np.int32).reshape(-1, 4)
-        ss = np.asarray(slotStart, dtype=np.int64)
-        out = np.full(self.slot.shape, -1, dtype=np.int32)
-        for t in range(self.numTrees):
-            slot = self.slot[t]
-            ok = np.nonzero((slot >= 0) & (slot < ss[t + 1] - ss[t]))[0]
-            e = table[ss[t] + slot[ok]]
-            split = e[:, 0] >= 0
-            ok, e = ok[split], e[split]
-            b = self.image[ok, e[:, 0]].astype(np.int32)
-            out[t, ok] = np.where(b <= e[:, 1], e[:, 2], e[:, 3])
-        self.slot = out
+            bag_counts(seed, numTrees, int(self.X.shape[0]), table, self.rowOffset)
 
 
 # ---------------------------------------------------------------------- models

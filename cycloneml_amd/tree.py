@@ -11,13 +11,21 @@ may still split gets its histogram feature x bin x stats over its rows, the
 best split of every node is found on the host (best_splits) and the rows move
 to the children.  Node indices: root 1, children 2 i and 2 i + 1.
 
-The level loop takes its step as an object with check(), totals(),
-sample(rows), bin(thresholds), histogram(nodeOf, K, B) and route(table): DeviceStep (the kernels; histograms go through
+One level loop (prepare_step, then grow_prepared) grows a tree, a forest
+(forest.py) and every tree of a boosted fit (gbt.py): it is level-synchronous
+over numTrees trees, with an optional bag and an optional feature subset per
+node; grow is the loop with one tree, all features and no bag.  It takes its
+step as an object with check(), totals(), sample(rows), bin(thresholds),
+bag(numTrees, table, seed), histogram(t0, t1, slotStart, nodeOf, K, B, nodeFeat,
+m) over the trees [t0, t1) and route(slotStart, table) over all trees: DeviceStep
+(the kernels of one unbagged tree over all features; histograms go through
 parallel.allreduce_ once per call, so every rank calls fit) and NumpyStep (host
-rows) are interchangeable.  Every row has a slot, a compact id of its node; -1
-is the skip slot of rows parked in leaves.  nodeOf names per slot its node 0 ..
-K - 1 of one histogram call or -1; table is (numSlots x 4) int32 (feature,
-splitBin, leftNew, rightNew) per slot, feature -1 for a slot whose rows park.
+rows, any number of trees) are interchangeable.  Every (tree, row) pair has a
+slot, a compact id of the row's node in that tree; -1 is the skip slot of rows
+parked in leaves.  Per-tree tables are concatenated: tree t's slots are the
+entries slotStart[t] .. slotStart[t + 1].  nodeOf names per slot entry its node
+0 .. K - 1 of one histogram call or -1; table is int32 (feature, splitBin,
+leftNew, rightNew) per slot entry, feature -1 for a slot whose rows park.
 
 This project's own rules: the sample of find_splits is every row when the
 sampling fraction min(max(maxBins^2, 10000) / n, 1) is 1 and otherwise
@@ -294,46 +302,64 @@ def prune(node: Node) -> Node:
     return node
 
 
-def nodes_per_call(d: int, B: int, S: int, maxNodes: int = MAX_NODES) -> int:
-    return int(min(maxNodes, max(1, HIST_BYTES // (8 * d * B * S))))
+def nodes_per_call(m: int, B: int, S: int, maxNodes: int = MAX_NODES) -> int:
+    """The nodes of one histogram call over m features per node."""
+    return int(min(maxNodes, MAX_NODES, max(1, HIST_BYTES // (8 * m * B * S))))
 
 
-def grow(step, d: int, numClasses: int, impurity: str, maxDepth: int = 5, maxBins: int = 32,
-         minInstancesPerNode: int = 1, minWeightFractionPerNode: float = 0.0,
-         minInfoGain: float = 0.0, seed: int = 0, pruneTree: bool = True):
-    """The level loop over `step`: (root Node, thresholds)."""
-    check_params(maxDepth, maxBins, minInstancesPerNode, minWeightFractionPerNode, minInfoGain,
-                 impurity, bool(numClasses))
+def prepare_step(step, maxBins: int, seed: int):
+    """What a fit does once with its rows: the rows' checks, the totals, the
+    split candidates from the sample and the binned image.  (thresholds, n, the
+    un-bagged sum of the weights)."""
     step.check()
     n, wsum = step.totals()
     _require(n > 0, "DecisionTree requires size of input RDD > 0, but was given by empty one.")
     thresholds = all_splits(*step.sample(sample_rows(maxBins, n, seed)), maxBins, n, wsum)
+    step.bin(thresholds)
+    return thresholds, n, wsum
+
+
+def grow_prepared(step, d: int, numClasses: int, impurity: str, numTrees: int,
+                  numFeaturesPerNode: int, thresholds, wsum: float, maxDepth: int = 5,
+                  minInstancesPerNode: int = 1, minWeightFractionPerNode: float = 0.0,
+                  minInfoGain: float = 0.0, bagTable=None, subsetOf=None, seed: int = 0,
+                  pruneTree: bool = True, nodesPerCall=None):
+    """The bag and the level loop over a step that prepare_step has binned: the
+    roots in tree order.  bagTable: the table of the bag's counts (None: every
+    row once); subsetOf(tree, node): the numFeaturesPerNode features of a node,
+    ascending (None: every node takes all d features)."""
+    m, nt = int(numFeaturesPerNode), int(numTrees)
     numSplits = np.array([len(t) for t in thresholds], dtype=np.int64)
     B = int(numSplits.max()) + 1
     S = num_stats(numClasses)
-    step.bin(thresholds)
+    step.bag(nt, bagTable, seed)
     minWeight = float(minWeightFractionPerNode) * wsum
-    per_call = nodes_per_call(d, B, S, getattr(step, "maxNodes", MAX_NODES))
-    nodes = {}
-    live = {1: 0}               # the nodes to split at this level -> their slot
+    per_call = int(nodesPerCall) if nodesPerCall else \
+        nodes_per_call(m, B, S, getattr(step, "maxNodes", MAX_NODES))
+    nodes = [{} for _ in range(nt)]
+    live = [{1: 0} for _ in range(nt)]      # per tree: the nodes to split at this level -> slot
     level = 0
-    while live:
-        order = sorted(live)
-        numSlots = len(order)
-        table = np.full((numSlots, 4), -1, dtype=np.int32)
-        nxt = {}
+    while any(live):
+        slotStart = np.zeros(nt + 1, dtype=np.int32)
+        slotStart[1:] = np.cumsum([len(lv) for lv in live])
+        table = np.full((int(slotStart[nt]), 4), -1, dtype=np.int32)
+        order = [(t, i) for t in range(nt) for i in sorted(live[t])]
+        nxt = [{} for _ in range(nt)]
         for g0 in range(0, len(order), per_call):
             group = order[g0:g0 + per_call]
-            nodeOf = np.full(numSlots, -1, dtype=np.int32)
-            for j, i in enumerate(group):
-                nodeOf[live[i]] = j
-            hist = step.histogram(nodeOf, len(group), B)
+            t0, t1 = group[0][0], group[-1][0] + 1
+            ss = (slotStart[t0:t1 + 1] - slotStart[t0]).astype(np.int32)
+            nodeOf = np.full(int(ss[-1]), -1, dtype=np.int32)
+            for j, (t, i) in enumerate(group):
+                nodeOf[ss[t - t0] + live[t][i]] = j
+            feats = None if subsetOf is None else np.stack([subsetOf(t, i) for t, i in group])
+            hist = step.histogram(t0, t1, ss, nodeOf, len(group), B, feats, m)
             best = best_splits(hist, numSplits, numClasses, impurity, minInstancesPerNode,
-                               minWeight, minInfoGain)
-            for j, i in enumerate(group):
-                if i not in nodes:      # the root: its statistics are the first evaluation's
-                    nodes[i] = Node(best.parent[j], best.impurity[j], numClasses)
-                node = nodes[i]
+                               minWeight, minInfoGain, features=feats)
+            for j, (t, i) in enumerate(group):
+                if i not in nodes[t]:   # the root: its statistics are the first evaluation's
+                    nodes[t][i] = Node(best.parent[j], best.impurity[j], numClasses)
+                node = nodes[t][i]
                 gain = float(best.gain[j])
                 if gain <= 0.0 or level == maxDepth:
                     continue
@@ -342,21 +368,34 @@ def grow(step, d: int, numClasses: int, impurity: str, maxDepth: int = 5, maxBin
                 node.split = (f, float(thresholds[f][s]))
                 node.left = Node(best.left[j], best.leftImp[j], numClasses)
                 node.right = Node(best.right[j], best.rightImp[j], numClasses)
-                nodes[2 * i], nodes[2 * i + 1] = node.left, node.right
+                nodes[t][2 * i], nodes[t][2 * i + 1] = node.left, node.right
                 new = []
                 for child, idx in ((node.left, 2 * i), (node.right, 2 * i + 1)):
                     if level + 1 == maxDepth or abs(child.impurity) < EPSILON:
                         new.append(-1)
                     else:
-                        nxt[idx] = len(nxt)
-                        new.append(nxt[idx])
-                table[live[i]] = (f, s, new[0], new[1])
-        if nxt:
-            step.route(table)
+                        nxt[t][idx] = len(nxt[t])
+                        new.append(nxt[t][idx])
+                table[slotStart[t] + live[t][i]] = (f, s, new[0], new[1])
+        if any(nxt):
+            step.route(slotStart, table)
         live = nxt
         level += 1
-    root = nodes[1]
-    return (prune(root) if pruneTree else root), thresholds
+    roots = [nodes[t][1] for t in range(nt)]
+    return [prune(r) if pruneTree else r for r in roots]
+
+
+def grow(step, d: int, numClasses: int, impurity: str, maxDepth: int = 5, maxBins: int = 32,
+         minInstancesPerNode: int = 1, minWeightFractionPerNode: float = 0.0,
+         minInfoGain: float = 0.0, seed: int = 0, pruneTree: bool = True):
+    """One tree over `step`, all features, no bag: (root Node, thresholds)."""
+    check_params(maxDepth, maxBins, minInstancesPerNode, minWeightFractionPerNode, minInfoGain,
+                 impurity, bool(numClasses))
+    thresholds, _, wsum = prepare_step(step, maxBins, seed)
+    (root,) = grow_prepared(step, d, numClasses, impurity, 1, d, thresholds, wsum, maxDepth,
+                            minInstancesPerNode, minWeightFractionPerNode, minInfoGain,
+                            seed=seed, pruneTree=pruneTree)
+    return root, thresholds
 
 
 # ----------------------------------------------------------------------- steps
@@ -428,14 +467,7 @@ class DTPlan:
         return image
 
     def _image(self, image):
-        import torch
-        if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 \
-                or image.dim() != 2 or int(image.shape[1]) != self.numFeatures \
-                or not image.is_contiguous():
-            raise N.IllegalArgumentException(
-                f"requirement failed: the image must be contiguous uint8 (n x {self.numFeatures}) "
-                "on the device")
-        return int(image.shape[0])
+        return check_image(image, self.numFeatures)
 
     def route(self, image, slot, table):
         import torch
@@ -515,8 +547,21 @@ def check_rows(X, numFeatures=None, what: str = "model") -> int:
     return int(X.shape[0])
 
 
+def check_image(image, numFeatures) -> int:
+    """The row count of a binned image (n x numFeatures uint8) on the device."""
+    import torch
+    if not torch.is_tensor(image) or not image.is_cuda or image.dtype != torch.uint8 \
+            or image.dim() != 2 or int(image.shape[1]) != numFeatures \
+            or not image.is_contiguous():
+        raise N.IllegalArgumentException(
+            f"requirement failed: the image must be contiguous uint8 (n x {numFeatures}) "
+            "on the device")
+    return int(image.shape[0])
+
+
 class DeviceStep:
-    """The step over device rows (this rank's shard): the image and the slots
+    """The step over device rows (this rank's shard) for one unbagged tree over
+    all features (csrc/decision_tree.hip's kernels): the image and the slots
     live on the device, a histogram comes back merged over the ranks."""
 
     def __init__(self, X, y, weights=None, numClasses: int = 0, workspaceBytes: int = 0,
@@ -531,8 +576,7 @@ class DeviceStep:
         DTPlan._vector(y, n, torch.float64, "labels")
         if weights is not None:
             DTPlan._vector(weights, n, torch.float64, "weights")
-        self.image = None
-        self.slot = torch.zeros(n, dtype=torch.int32, device=X.device)
+        self.image = self.slot = None
 
     def check(self):
         from . import parallel
@@ -576,29 +620,36 @@ class DeviceStep:
     def bin(self, thresholds):
         self.image = self.plan.bin(self.X, thresholds)
 
-    def histogram(self, nodeOf, K, B):
+    def bag(self, numTrees: int, table, seed: int):
+        import torch
+        _require(int(numTrees) == 1 and table is None,
+                 "DeviceStep grows one tree without a bag; a forest takes ForestDeviceStep")
+        self.slot = torch.zeros(int(self.X.shape[0]), dtype=torch.int32, device=self.X.device)
+
+    def histogram(self, t0, t1, slotStart, nodeOf, K, B, nodeFeat, m):
         from . import parallel
+        _require((t0, t1) == (0, 1) and nodeFeat is None and m == self.d,
+                 "DeviceStep grows one tree over all features; a forest takes ForestDeviceStep")
         hist = self.plan.histogram(self.image, self.y, self.weights, self.slot, nodeOf, K, B)
         parallel.allreduce_(hist.view(-1))
         return hist.cpu().numpy()
 
-    def route(self, table):
+    def route(self, slotStart, table):
         self.plan.route(self.image, self.slot, table)
 
 
 class NumpyStep:
-    """The step over host rows in numpy: the same bins and routes as the
-    kernels, the sums in plain row order."""
+    """The step over host rows in numpy, for any number of unbagged trees: the
+    same bins and routes as the kernels, the sums in plain row order."""
 
     def __init__(self, X, y, weights=None, numClasses: int = 0):
         self.X = np.ascontiguousarray(X, dtype=np.float64)
         _require(self.X.ndim == 2, "rows must be n x d")
-        n, self.d = self.X.shape
+        self.d = int(self.X.shape[1])
         self.y = np.ascontiguousarray(y, dtype=np.float64)
         self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
         self.numClasses = int(numClasses)
-        self.image = None
-        self.slot = np.zeros(n, dtype=np.int32)
+        self.image = self.slot = self.bagCounts = None      # slot: numTrees x n, set by bag()
 
     def check(self):
         C = self.numClasses
@@ -644,36 +695,54 @@ class NumpyStep:
         for f, t in enumerate(thresholds):
             self.image[:, f] = np.searchsorted(np.asarray(t, dtype=np.float64), self.X[:, f], "left")
 
-    def histogram(self, nodeOf, K, B):
+    def bag(self, numTrees: int, table, seed: int):
+        _require(table is None, "NumpyStep draws no bag; a bagged fit takes ForestNumpyStep")
+        self.slot = np.zeros((int(numTrees), int(self.X.shape[0])), dtype=np.int32)
+
+    def histogram(self, t0, t1, slotStart, nodeOf, K, B, nodeFeat, m):
         nodeOf = np.asarray(nodeOf, dtype=np.int64)
-        C, d = self.numClasses, self.d
+        ss = np.asarray(slotStart, dtype=np.int64)
+        C = self.numClasses
         S = num_stats(C)
-        hist = np.zeros((K, d, B, S), dtype=np.float64)
-        live = np.nonzero(self.slot >= 0)[0]
-        node = nodeOf[self.slot[live]]
-        live, node = live[node >= 0], node[node >= 0]
-        w = np.ones(live.size) if self.weights is None else self.weights[live]
-        y = self.y[live]
-        if C:
-            vals = [(y.astype(np.int64), w), (np.full(live.size, C), np.ones(live.size))]
-        else:
-            wy = w * y
-            vals = [(np.full(live.size, s), v) for s, v in enumerate((w, wy, wy * y, np.ones(live.size)))]
-        for f in range(d):
-            b = self.image[live, f].astype(np.int64)
-            for s, v in vals:
-                np.add.at(hist, (node, f, b, s), v)      # unbuffered: row order
+        feats = np.broadcast_to(np.arange(self.d), (K, self.d)) if nodeFeat is None else \
+            np.asarray(nodeFeat, dtype=np.int64).reshape(K, m)
+        hist = np.zeros((K, m, B, S), dtype=np.float64)
+        for t in range(t0, t1):
+            slot = self.slot[t]
+            rows = np.nonzero((slot >= 0) & (slot < ss[t - t0 + 1] - ss[t - t0]))[0]
+            node = nodeOf[ss[t - t0] + slot[rows]]
+            keep = node >= 0
+            if self.bagCounts is not None:
+                keep &= self.bagCounts[t, rows] > 0     # a row drawn 0 times is not loaded
+            rows, node = rows[keep], node[keep]
+            # without a bag every count is 1.0, and 1.0 w is w to the bit
+            cnt = np.ones(rows.size) if self.bagCounts is None else \
+                self.bagCounts[t, rows].astype(np.float64)
+            iw = cnt * (np.ones(rows.size) if self.weights is None else self.weights[rows])
+            y = self.y[rows]
+            if C:
+                vals = [(y.astype(np.int64), iw), (np.full(rows.size, C), cnt)]
+            else:
+                wy = iw * y
+                vals = [(np.full(rows.size, s), v) for s, v in enumerate((iw, wy, wy * y, cnt))]
+            for j in range(m):
+                b = self.image[rows, feats[node, j]].astype(np.int64)
+                for s, v in vals:
+                    np.add.at(hist, (node, j, b, s), v)      # unbuffered: row order
         return hist
 
-    def route(self, table):
+    def route(self, slotStart, table):
         table = np.asarray(table, dtype=np.int32).reshape(-1, 4)
-        out = np.full(self.slot.size, -1, dtype=np.int32)
-        ok = np.nonzero((self.slot >= 0) & (self.slot < table.shape[0]))[0]
-        t = table[self.slot[ok]]
-        split = t[:, 0] >= 0
-        ok, t = ok[split], t[split]
-        b = self.image[ok, t[:, 0]].astype(np.int32)
-        out[ok] = np.where(b <= t[:, 1], t[:, 2], t[:, 3])
+        ss = np.asarray(slotStart, dtype=np.int64)
+        out = np.full(self.slot.shape, -1, dtype=np.int32)
+        for t in range(self.slot.shape[0]):
+            slot = self.slot[t]
+            ok = np.nonzero((slot >= 0) & (slot < ss[t + 1] - ss[t]))[0]
+            e = table[ss[t] + slot[ok]]
+            split = e[:, 0] >= 0
+            ok, e = ok[split], e[split]
+            b = self.image[ok, e[:, 0]].astype(np.int32)
+            out[t, ok] = np.where(b <= e[:, 1], e[:, 2], e[:, 3])
         self.slot = out
 
 

@@ -233,9 +233,9 @@ def test_route(cuda):
     at = np.nonzero((slot[:40] == 0))[0]
     assert at.size and np.all(got[at] == 0)
     ns = NumpyStep(np.zeros((n, d)), np.zeros(n), None, 2)
-    ns.image, ns.slot = image, slot.copy()
-    ns.route(table)
-    assert np.array_equal(ns.slot, ref)
+    ns.image, ns.slot = image, slot.copy()[None]          # one tree
+    ns.route(np.array([0, 4], dtype=np.int32), table)
+    assert np.array_equal(ns.slot[0], ref)
 
 
 # --------------------------------------------------------------------- predict
