@@ -59,6 +59,13 @@ from .gbt import (  # noqa: F401
     GBTRegressionModel,
     GBTRegressor,
 )
+from .fm import (  # noqa: F401
+    FMClassificationModel,
+    FMClassifier,
+    FMPlan,
+    FMRegressionModel,
+    FMRegressor,
+)
 from .regression_summary import (  # noqa: F401
     LinearRegressionSummary,
     LinearRegressionTrainingSummary,

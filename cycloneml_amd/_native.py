@@ -184,6 +184,16 @@ SIGNATURES = {
     "cyc_mlp_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_mlp_loss_grad_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "cyc_mlp_forward_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_fm_run_rows": (ctypes.c_int, []),
+    "cyc_fm_tile_rows": (ctypes.c_int, []),
+    "cyc_fm_max_factors": (ctypes.c_int, []),
+    "cyc_fm_max_features": (ctypes.c_int, []),
+    "cyc_fm_fused_features": (ctypes.c_int, [_i32]),
+    "cyc_fm_plan_create": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i64,
+                                          ctypes.POINTER(_vp)]),
+    "cyc_fm_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_fm_evaluate_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _i64, _vp, _vp]),
+    "cyc_fm_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cyc_gmm_plan_create": (ctypes.c_int, [_i32, _i32, _i64, ctypes.POINTER(_vp)]),
     "cyc_gmm_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_gmm_set_model_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -22,6 +22,7 @@ integer.
 from __future__ import annotations
 
 import math
+import struct
 
 import numpy as np
 
@@ -42,14 +43,54 @@ def _i64(v: int) -> int:
     return v - (1 << 64) if v >= 1 << 63 else v
 
 
+def strict_log(x: float) -> float:
+    """StrictMath.log of a positive normal double: fdlibm's __ieee754_log
+    (e_log.c), which a platform's libm log differs from by an ulp now and then."""
+    ln2_hi, ln2_lo = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+    Lg1, Lg2, Lg3 = 6.666666666666735130e-01, 3.999999999940941908e-01, 2.857142874366239149e-01
+    Lg4, Lg5, Lg6 = 2.222219843214978396e-01, 1.818357216161805012e-01, 1.531383769920937332e-01
+    Lg7 = 1.479819860511658591e-01
+    bits = struct.unpack("<q", struct.pack("<d", x))[0]
+    hx, lx = (bits >> 32) & 0xFFFFFFFF, bits & 0xFFFFFFFF
+    if not 0x00100000 <= hx < 0x7FF00000:
+        raise ValueError("strict_log takes a positive normal double")
+    k = (hx >> 20) - 1023
+    hx &= 0x000FFFFF
+    i = (hx + 0x95F64) & 0x100000
+    x = struct.unpack("<d", struct.pack("<q", ((hx | (i ^ 0x3FF00000)) << 32) | lx))[0]
+    k += i >> 20
+    f = x - 1.0
+    if (0x000FFFFF & (2 + hx)) < 3:                 # |f| < 2^-20
+        if f == 0.0:
+            return 0.0 if k == 0 else k * ln2_hi + k * ln2_lo
+        R = f * f * (0.5 - 0.33333333333333333 * f)
+        return f - R if k == 0 else k * ln2_hi - ((R - k * ln2_lo) - f)
+    s = f / (2.0 + f)
+    dk, z = float(k), s * s
+    w = z * z
+    t1 = w * (Lg2 + w * (Lg4 + w * Lg6))
+    t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)))
+    R = t2 + t1
+    if ((hx - 0x6147A) | (0x6B851 - hx)) > 0:
+        hfsq = 0.5 * f * f
+        if k == 0:
+            return f - (hfsq - s * (hfsq + R))
+        return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f)
+    if k == 0:
+        return f - s * (f - R)
+    return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f)
+
+
 class JavaRandom:
     """java.util.Random (the 48-bit LCG); scala.util.Random delegates to it."""
 
     def __init__(self, seed: int):
+        self._nextGaussian = None
         self.set_seed(seed)
 
     def set_seed(self, seed: int):
         self._s = (int(seed) ^ 0x5DEECE66D) & _M48
+        self._nextGaussian = None
 
     def next(self, bits: int) -> int:
         self._s = (self._s * 0x5DEECE66D + 0xB) & _M48
@@ -76,6 +117,22 @@ class JavaRandom:
 
     def next_double(self) -> float:
         return ((self.next(26) << 27) + self.next(27)) * (1.0 / (1 << 53))
+
+    def next_gaussian(self) -> float:
+        """The polar method with its cached second value; StrictMath.sqrt is
+        math.sqrt (both correctly rounded), StrictMath.log is strict_log."""
+        if self._nextGaussian is not None:
+            g, self._nextGaussian = self._nextGaussian, None
+            return g
+        while True:
+            v1 = 2 * self.next_double() - 1
+            v2 = 2 * self.next_double() - 1
+            s = v1 * v1 + v2 * v2
+            if 0 < s < 1:
+                break
+        multiplier = math.sqrt(-2 * strict_log(s) / s)
+        self._nextGaussian = v2 * multiplier
+        return v1 * multiplier
 
 
 class XORShiftRandom(JavaRandom):

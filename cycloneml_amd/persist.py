@@ -512,3 +512,50 @@ def load_naive_bayes_model(path):
                         float(params.get("smoothing", 1.0)))
     m.uid = meta.get("uid")
     return m
+
+
+# -- ml FMRegressionModel / FMClassificationModel -------------------------------
+
+FM_REGRESSION_CLASS = "org.apache.spark.ml.regression.FMRegressionModel"
+FM_CLASSIFICATION_CLASS = "org.apache.spark.ml.classification.FMClassificationModel"
+
+
+def save_fm_model(model, path, uid=None, overwrite=False):
+    """FMRegressionModelWriter / FMClassificationModelWriter.saveImpl: data/ =
+    one parquet row Data(intercept: Double, linear: Vector, factors: Matrix)."""
+    from .fm import FMClassificationModel
+    pa, _ = _pa()
+    _check_new_path(path, overwrite)
+    classifier = isinstance(model, FMClassificationModel)
+    meta = {"class": FM_CLASSIFICATION_CLASS if classifier else FM_REGRESSION_CLASS,
+            "timestamp": int(time.time() * 1000), "sparkVersion": SPARK_VERSION,
+            "uid": uid or f"{'fmc' if classifier else 'fmr'}_{uuid.uuid4().hex[:12]}",
+            "paramMap": {}, "defaultParamMap": {}}
+    _write_text(os.path.join(path, "metadata"), json.dumps(meta, separators=(",", ":")))
+    fields = [pa.field("intercept", pa.float64(), nullable=False),
+              pa.field("linear", _arrow_vector()), pa.field("factors", _arrow_matrix())]
+    spark = [_field("intercept", "double", False), _field("linear", _udt("vector")),
+             _field("factors", _udt("matrix"))]
+    _write_parquet(os.path.join(path, "data"), fields, spark,
+                   [{"intercept": float(model.intercept),
+                     "linear": encode_dense_vector(model.linear),
+                     "factors": encode_dense_matrix(model.factors)}])
+
+
+def load_fm_model(path):
+    from .fm import FMClassificationModel, FMRegressionModel
+    meta = json.loads(_read_text(os.path.join(path, "metadata")))
+    kinds = {FM_REGRESSION_CLASS: FMRegressionModel,
+             FM_CLASSIFICATION_CLASS: FMClassificationModel}
+    if meta.get("class") not in kinds:
+        raise ValueError(f"requirement failed: Error loading metadata: Expected class name "
+                         f"{FM_REGRESSION_CLASS} or {FM_CLASSIFICATION_CLASS} but found class "
+                         f"name {meta.get('class')}")
+    rows = _read_parquet_rows(os.path.join(path, "data"))
+    if len(rows) != 1:
+        raise ValueError("expected one data row")
+    r = rows[0]
+    m = kinds[meta["class"]](r["intercept"], decode_vector(r["linear"]),
+                             decode_matrix(r["factors"]))
+    m.uid = meta.get("uid")
+    return m

@@ -1155,6 +1155,55 @@ int cyc_gbt_predict_dev(cyc_gbt_plan plan, const double* X, int64_t nrows, int32
                         int32_t classifier, int32_t* leaf, double* margin, double* raw,
                         double* prob, double* pred, void* stream);
 
+/* ------------------------------------------- FMRegressor / FMClassifier */
+/* One evaluation of the factorization machine's loss and gradient
+ * (ml/regression/FMRegressor.scala, BaseFactorizationMachinesGradient) over
+ * dense fp64 device rows, and the models' forward.  A plan holds numFeatures
+ * d (1 .. cyc_fm_max_features), factorSize k (1 .. cyc_fm_max_factors), the
+ * two fit flags, the loss (0 squared, 1 logistic with labels 0 / 1) and the
+ * scratch of the calls (workspaceBytes for the runs in flight; 0: 256 MiB).
+ *
+ * coef (device) = [V (d x k row-major: V[i,f] at i k + f) | w (d, only with
+ * fitLinear) | b (1, only with fitIntercept)].  Per row raw = b + sum w_i x_i
+ * + sum_f 0.5 (s_f s_f - q_f), s_f = sum_i V[i,f] x_i, q_f = sum_i (V[i,f]
+ * x_i)^2; squared: loss (raw - y)^2, m = 2 (raw - y); logistic: p = 1 / (1 +
+ * exp(-raw)), loss y > 0 ? log1pExp(-raw) : log1pExp(raw), m = p - y.
+ *
+ * cyc_fm_evaluate_dev SETS out (device, the coefficients' length + 2) = [G |
+ * L | cnt]: G = sum over the rows taken of m (x_i s_f - V[i,f] x_i x_i | x_i |
+ * 1) in coef's layout, L the sum of their losses, cnt their number.  Row r of
+ * the shard is global row rowOffset + r; with fraction < 1 global row g is
+ * taken in iteration iter iff the top 53 bits of the forest's mix(42 + iter,
+ * 0, 0, g) are >= floor((1 - fraction) 2^53); a row that is not taken is not
+ * loaded.  The rows are cut into runs of cyc_fm_run_rows rows; a run is summed
+ * in tiles of cyc_fm_tile_rows rows and the runs are added in order, so out
+ * has the same bytes on every call and for every workspace size (fp64 MFMA,
+ * no floating-point atomics).  d <= cyc_fm_fused_features(k) (0 for a bad k)
+ * takes the fused kernel that reads X once; a wider d the two-pass form.  A
+ * logistic plan fails the call for a label other than 0 / 1, naming the
+ * lowest such global row (it synchronizes the stream to read that row; out is
+ * then undefined).
+ *
+ * cyc_fm_predict_dev: margin (nrows) = raw, raw (nrows x 2) = (-raw, raw),
+ * prob (nrows x 2) = (1 - p, p), pred (nrows) = raw for the squared loss and
+ * raw > 0 ? 1 : 0 for the logistic one; any may be NULL, not all; raw and
+ * prob need a logistic plan.  It does not synchronize. */
+typedef struct cyc_fm_plan_s* cyc_fm_plan;
+
+int cyc_fm_run_rows(void);
+int cyc_fm_tile_rows(void);
+int cyc_fm_max_factors(void);
+int cyc_fm_max_features(void);
+int cyc_fm_fused_features(int32_t factorSize);
+int cyc_fm_plan_create(int32_t numFeatures, int32_t factorSize, int32_t fitIntercept,
+                       int32_t fitLinear, int32_t loss, int64_t workspaceBytes, cyc_fm_plan* plan);
+int cyc_fm_plan_destroy(cyc_fm_plan plan);
+int cyc_fm_evaluate_dev(cyc_fm_plan plan, const double* X, const double* y, int64_t nrows,
+                        const double* coef, int64_t iter, double fraction, int64_t rowOffset,
+                        double* out, void* stream);
+int cyc_fm_predict_dev(cyc_fm_plan plan, const double* X, int64_t nrows, const double* coef,
+                       double* margin, double* raw, double* prob, double* pred, void* stream);
+
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
  * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
