@@ -65,6 +65,7 @@ from .fm import (  # noqa: F401
     FMPlan,
     FMRegressionModel,
     FMRegressor,
+    FMSparseRows,
 )
 from .regression_summary import (  # noqa: F401
     LinearRegressionSummary,

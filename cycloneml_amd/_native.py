@@ -194,6 +194,12 @@ SIGNATURES = {
     "cyc_fm_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_fm_evaluate_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _i64, _vp, _vp]),
     "cyc_fm_predict_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_fmcsr_segment_entries": (ctypes.c_int, []),
+    "cyc_fmcsr_rows_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp,
+                                             ctypes.POINTER(_vp)]),
+    "cyc_fmcsr_rows_destroy": (ctypes.c_int, [_vp]),
+    "cyc_fmcsr_evaluate_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _f64, _i64, _vp, _vp]),
+    "cyc_fmcsr_predict_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cyc_gmm_plan_create": (ctypes.c_int, [_i32, _i32, _i64, ctypes.POINTER(_vp)]),
     "cyc_gmm_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_gmm_set_model_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

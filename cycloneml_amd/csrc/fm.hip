@@ -53,57 +53,29 @@
 //   k_fm_fold, k_fm_finish
 // No atomics on doubles, every sum has one fixed order: the same bytes on
 // every call and for every workspace size.  The only atomic is the integer
-// atomicMin of the lowest row whose label is not 0 / 1.
+// atomicMin of the lowest row whose label is not 0 / 1.  The plan, the batch
+// rule and the row epilogue are fm_dev.hpp's, shared with fm_csr.hip (CSR rows).
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <mutex>
 #include <string>
 
-#include "binary_rows.hpp"
-#include "common.hpp"
+#include "fm_dev.hpp"
 #include "row_gemm.hpp"
-
-struct cyc_fm_plan_s {
-  std::mutex mu;
-  int d = 0, k = 0;
-  int fitIntercept = 0, fitLinear = 0, loss = 0;
-  int64_t wsBytes = 0;
-  cyc::DeviceBuffer dense, image, accum, ws, bad;
-};
 
 namespace {
 
 using namespace cyc::rowgemm;
+using namespace cyc::fmdev;
 
 constexpr int kFmTileRows = 16;
-constexpr int kFmRunRows = 1024;
-constexpr int kMaxFactors = 64;
 constexpr int kMaxFmFeatures = 65535;
 constexpr int64_t kDefaultWorkspace = (int64_t)256 << 20;
 constexpr int64_t kMaxRunsPerRound = 1 << 20;
-constexpr uint64_t kFmGolden = 0x9E3779B97F4A7C15ull;
-constexpr uint64_t kNoBadRow = 0x7f7f7f7f7f7f7f7full;   // memset(0x7f)
-constexpr int kLossSquared = 0, kLossLogistic = 1;
 
 typedef double double2_a16 __attribute__((ext_vector_type(2), aligned(16)));
-
-// forest.py's mix(), the batch rule: row r of iteration i is taken iff the top
-// 53 bits of mix(42 + i, 0, 0, r) are >= floor((1 - fraction) 2^53)
-__host__ __device__ __forceinline__ uint64_t fm_fin(uint64_t z) {
-  z ^= z >> 30;
-  z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27;
-  z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ bool fm_take(uint64_t h1, uint64_t thr, int64_t globalRow) {
-  return (fm_fin(h1 + kFmGolden * ((uint64_t)globalRow + 1ull)) >> 11) >= thr;
-}
 
 inline int fm_kt(int k) { return tiles16(k + 1); }
 inline int fm_fused_features(int k) { return 64 * (16 / fm_kt(k)); }
@@ -123,30 +95,6 @@ __global__ __launch_bounds__(256) void k_fm_operands(const double* __restrict__ 
     W[e] = c < k ? v : (w ? w[i] : 0.0);
     W[total + e] = v * v;
   }
-}
-
-// raw of one row from its finished products: S1 = x [V | w], S2 = x^2 V^2
-__device__ __forceinline__ double fm_raw(const double* S1, const double* S2, int k, double b) {
-  double raw = b + S1[k];
-  for (int f = 0; f < k; ++f) {
-    const double s = S1[f];
-    raw += 0.5 * (s * s - S2[f]);
-  }
-  return raw;
-}
-
-// loss and multiplier; false: a classifier's label that is not 0 / 1
-__device__ __forceinline__ bool fm_loss(int loss, double raw, double y, double* l, double* m) {
-  if (loss == kLossSquared) {
-    const double diff = raw - y;
-    *l = diff * diff;
-    *m = 2.0 * diff;
-    return true;
-  }
-  if (!(y == 0.0 || y == 1.0)) return false;
-  *l = y > 0 ? cyc::log1p_exp(-raw) : cyc::log1p_exp(raw);
-  *m = 1.0 / (1.0 + exp(-raw)) - y;
-  return true;
 }
 
 // ------------------------------------------------------------- the fused form
@@ -257,7 +205,7 @@ __global__ __launch_bounds__(256) void k_fm_step(
           cntAcc += 1.0;
           gbAcc += mm;
         } else {
-          atomicMin(bad, (unsigned long long)(firstRow + t0 + tid));
+          fm_flag_bad(bad, firstRow + t0 + tid);
         }
       }
       mrow[tid] = m;
@@ -407,7 +355,7 @@ __global__ __launch_bounds__(256) void k_fm_forward(
             cnt = 1.0;
           } else {
             l = 0.0;
-            atomicMin(bad, (unsigned long long)(firstRow + row));
+            fm_flag_bad(bad, firstRow + row);
           }
         }
         mrow[lane] = m;
@@ -586,15 +534,11 @@ int allow_lds(K kernel, size_t bytes) {
     default: { constexpr int KT = 5; CALL; } break; \
   }
 
-struct Coef {
-  const double *V, *w, *b;
-};
-Coef split_coef(const cyc_fm_plan_s* p, const double* coef) {
-  const int64_t dk = (int64_t)p->d * p->k;
-  Coef c{coef, nullptr, nullptr};
-  if (p->fitLinear) c.w = coef + dk;
-  if (p->fitIntercept) c.b = coef + dk + (p->fitLinear ? p->d : 0);
-  return c;
+// the dense kernels' limit (a plan itself may hold any d, for CSR rows)
+int check_dense_features(const cyc_fm_plan_s* p) {
+  CYC_REQUIRE(p->d <= kMaxFmFeatures, "FM supports 1 to " + std::to_string(kMaxFmFeatures) +
+                                          " features but got " + std::to_string(p->d));
+  return CYC_OK;
 }
 
 // the two operand images of this call's coefficients
@@ -624,9 +568,10 @@ int cyc_fm_fused_features(int32_t factorSize) {
 int cyc_fm_plan_create(int32_t numFeatures, int32_t factorSize, int32_t fitIntercept,
                        int32_t fitLinear, int32_t loss, int64_t workspaceBytes, cyc_fm_plan* plan) {
   CYC_REQUIRE(plan != nullptr, "plan must not be null");
-  CYC_REQUIRE(numFeatures >= 1 && numFeatures <= kMaxFmFeatures,
-              "FM supports 1 to " + std::to_string(kMaxFmFeatures) + " features but got " +
-                  std::to_string(numFeatures));
+  // the dense calls refuse d > cyc_fm_max_features themselves; CSR rows
+  // (fm_csr.hip) take any d
+  CYC_REQUIRE(numFeatures >= 1, "FM needs at least one feature but got " +
+                                    std::to_string(numFeatures));
   CYC_REQUIRE(factorSize >= 1 && factorSize <= kMaxFactors,
               "factorSize must be in [1, " + std::to_string(kMaxFactors) + "] but got " +
                   std::to_string(factorSize));
@@ -657,29 +602,24 @@ int cyc_fm_plan_destroy(cyc_fm_plan plan) {
 int cyc_fm_evaluate_dev(cyc_fm_plan plan, const double* X, const double* y, int64_t nrows,
                         const double* coef, int64_t iter, double fraction, int64_t rowOffset,
                         double* out, void* stream) {
-  CYC_REQUIRE(plan != nullptr, "plan must not be null");
-  CYC_REQUIRE(nrows >= 0 && rowOffset >= 0, "nrows >= 0 and rowOffset >= 0");
-  CYC_REQUIRE(coef != nullptr && out != nullptr, "coef and out must not be null");
-  CYC_REQUIRE(fraction > 0.0 && fraction <= 1.0,
-              "miniBatchFraction must be in (0, 1] but got " + cyc::java_double(fraction));
+  if (int rc = fm_check_evaluate(plan, nrows, rowOffset, coef, out, fraction)) return rc;
   CYC_REQUIRE(nrows == 0 || (X != nullptr && y != nullptr), "non-null rows and labels");
   cyc_fm_plan_s* p = plan;
+  if (int rc = check_dense_features(p)) return rc;
   hipStream_t st = cyc::as_stream(stream);
   std::lock_guard<std::mutex> guard(p->mu);
   const int d = p->d, k = p->k, KTv = fm_kt(k);
   const int64_t len = (int64_t)d * (k + 2) + 3, imgLen = packed_len(d, k + 1);
   const Coef c = split_coef(p, coef);
   if (int rc = p->accum.reserve(sizeof(double) * (size_t)len)) return rc;
-  if (int rc = p->bad.reserve(sizeof(unsigned long long))) return rc;
   CYC_HIP(hipMemsetAsync(p->accum.ptr, 0, sizeof(double) * (size_t)len, st));
-  CYC_HIP(hipMemsetAsync(p->bad.ptr, 0x7f, sizeof(unsigned long long), st));
+  if (int rc = fm_clear_bad(p, st)) return rc;
   double* accum = (double*)p->accum.ptr;
   auto* bad = (unsigned long long*)p->bad.ptr;
   if (nrows > 0) {
     if (int rc = pack_operands(p, c, st)) return rc;
     const double* Bp = (const double*)p->image.ptr;
-    const uint64_t thr = (uint64_t)std::floor((1.0 - fraction) * 9007199254740992.0);
-    const uint64_t h1 = fm_fin(fm_fin((uint64_t)(42 + iter) + kFmGolden) + kFmGolden);
+    const uint64_t thr = fm_threshold(fraction), h1 = fm_seed(iter);
     const bool fused = d <= fm_fused_features(k);
     // a run in flight: its partial, and in the two-pass form its rows of M and aux
     const int64_t perRun = sizeof(double) * (len + (fused ? 0 : (int64_t)kFmRunRows * (k + 3)));
@@ -734,14 +674,7 @@ int cyc_fm_evaluate_dev(cyc_fm_plan plan, const double* X, const double* y, int6
   hipLaunchKernelGGL(k_fm_finish, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)),
                      dim3(256), 0, st, accum, c.V, d, k, p->fitLinear, p->fitIntercept, out);
   CYC_LAUNCH_CHECK("k_fm_finish");
-  if (p->loss == kLossLogistic && nrows > 0) {
-    unsigned long long row = kNoBadRow;
-    CYC_HIP(hipMemcpyAsync(&row, bad, sizeof(row), hipMemcpyDeviceToHost, st));
-    CYC_HIP(hipStreamSynchronize(st));
-    CYC_REQUIRE(row == kNoBadRow, "Classification labels should be 0 or 1 but row " +
-                                      std::to_string(row) + " has another label");
-  }
-  return CYC_OK;
+  return nrows > 0 ? fm_report_bad(p, st) : CYC_OK;
 }
 
 int cyc_fm_predict_dev(cyc_fm_plan plan, const double* X, int64_t nrows, const double* coef,
@@ -754,6 +687,7 @@ int cyc_fm_predict_dev(cyc_fm_plan plan, const double* X, int64_t nrows, const d
   if (nrows == 0) return CYC_OK;
   CYC_REQUIRE(X != nullptr, "non-null rows");
   cyc_fm_plan_s* p = plan;
+  if (int rc = check_dense_features(p)) return rc;
   CYC_REQUIRE(p->loss == kLossLogistic || (raw == nullptr && prob == nullptr),
               "raw and prob need a classifier");
   hipStream_t st = cyc::as_stream(stream);

@@ -1,7 +1,10 @@
 """FMRegressor / FMClassifier (ml/regression/FMRegressor.scala, ml/classification/
 FMClassifier.scala and mllib/optimization/GradientDescent.scala, Spark 3.3) over
-dense fp64 device rows.  The kernels are csrc/fm.hip (cyc_fm_* in
-include/cyclone.h).
+device rows: dense fp64 (csrc/fm.hip, cyc_fm_* in include/cyclone.h, up to
+65 535 features) or CSR (linalg.CSRRows, or FMSparseRows prepared from them
+once; csrc/fm_csr.hip, cyc_fmcsr_*, any number of features, a stored zero
+contributes nothing).  The caller chooses the layout; every rank of one fit
+uses the same one.
 
 Coefficients: one flat fp64 vector [V (d x k row-major) | w (d, fitLinear) | b
 (1, fitIntercept)].  Per row, i and f ascending, every product rounded before its
@@ -35,9 +38,10 @@ This package's own rules: below miniBatchFraction 1 global row r is in batch i i
 the top 53 bits of forest.mix(42 + i, 0, 0, r) are >= forest.bernoulli_table(
 fraction)[0] (Spark's RDD.sample is not restated; fraction 1 reproduces Spark);
 the initial factors are java.util.Random(seed).nextGaussian() initStd with
-StrictMath.log / sqrt taken as math.log / math.sqrt.  Out of scope: CSR rows, a
-weight column, Spark's own mini-batch draws, thresholds, transform, factorSize
-above 64.
+StrictMath.log / sqrt taken as math.log / math.sqrt.  Out of scope: a weight
+column, Spark's own mini-batch draws, thresholds, transform, factorSize above
+64, an automatic choice between the dense and the CSR layout, a sparse gradient
+or allreduce, a CSR FMNumpyStep.
 """
 from __future__ import annotations
 
@@ -111,6 +115,47 @@ def batch_rows(i: int, fraction: float, n: int, rowOffset: int = 0):
     return u >= RF.bernoulli_table(fraction)[0]
 
 
+# ------------------------------------------------------------------------ rows
+class FMSparseRows:
+    """cyc_fmcsr_rows: a CSRRows shard prepared once for the CSR kernels (the
+    index check, the column-major copy and its segment table).  It keeps the
+    shard's arrays alive; a slice whose rowptr[0] > 0 is rebased here."""
+
+    def __init__(self, csr):
+        import torch
+        from .linalg import CSRRows
+        _require(isinstance(csr, CSRRows), "FMSparseRows takes CSRRows")
+        rowptr, colidx, values = csr.rowptr, csr.colidx, csr.values
+        _require(rowptr.is_cuda and rowptr.dtype == torch.int64 and colidx.dtype == torch.int32
+                 and values.dtype == torch.float64 and colidx.numel() == values.numel(),
+                 "CSR rows are int64 rowptr, int32 colidx and fp64 values on the device")
+        self.n, self.d, self.device = csr.n, csr.numCols, csr.device
+        base = int(rowptr[0]) if self.n > 0 else 0
+        if base:
+            rowptr = rowptr - base
+        self._arrays = (rowptr.contiguous(), colidx.contiguous(), values.contiguous())
+        self._lib = N.load()
+        self.segmentEntries = int(self._lib.cyc_fmcsr_segment_entries())
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            N.check(self._lib.cyc_fmcsr_rows_create(*(N.ptr(t) for t in self._arrays), self.n,
+                                                    self.d, N.stream_handle(), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.cyc_fmcsr_rows_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+
+def as_rows(X):
+    """Dense rows and FMSparseRows as they are; CSRRows prepared."""
+    from .linalg import CSRRows
+    return FMSparseRows(X) if isinstance(X, CSRRows) else X
+
+
 # ------------------------------------------------------------------------ plan
 class FMPlan:
     """cyc_fm_plan: the shape, the flags, the loss and the scratch of the calls."""
@@ -140,10 +185,10 @@ class FMPlan:
 
     def _rows(self, X) -> int:
         import torch
-        from .linalg import CSRRows
-        if isinstance(X, CSRRows):
-            raise N.IllegalArgumentException(
-                "FM takes dense rows; the CSR form is not provided")
+        if isinstance(X, FMSparseRows):
+            _require(X.d == self.d,
+                     f"the rows have {X.d} features but the plan has {self.d}")
+            return X.n
         _require(torch.is_tensor(X) and X.is_cuda and X.dtype == torch.float64 and X.dim() == 2
                  and X.is_contiguous(), "rows must be a contiguous fp64 device tensor (n x d)")
         _require(int(X.shape[1]) == self.d,
@@ -162,6 +207,7 @@ class FMPlan:
         """out (device, coefLen + 2) = [G | L | cnt] of batch `iter` of this
         shard, whose first row is global row rowOffset."""
         import torch
+        X = as_rows(X)
         n = self._rows(X)
         self._vector(y, n, "labels")
         self._vector(coef, self.coefLen, "coef")
@@ -169,6 +215,11 @@ class FMPlan:
             out = torch.empty(self.coefLen + 2, dtype=torch.float64, device=X.device)
         self._vector(out, self.coefLen + 2, "out")
         with torch.cuda.device(X.device):
+            if isinstance(X, FMSparseRows):
+                N.check(self._lib.cyc_fmcsr_evaluate_dev(
+                    self.handle, X.handle, N.ptr(y), N.ptr(coef), int(iter), float(fraction),
+                    int(rowOffset), N.ptr(out), N.stream_handle()))
+                return out
             N.check(self._lib.cyc_fm_evaluate_dev(self.handle, N.ptr(X), N.ptr(y), n, N.ptr(coef),
                                                   int(iter), float(fraction), int(rowOffset),
                                                   N.ptr(out), N.stream_handle()))
@@ -178,12 +229,18 @@ class FMPlan:
         """(margin n, raw n x 2, prob n x 2, pred n) device tensors (None for
         what is not asked for)."""
         import torch
+        X = as_rows(X)
         n = self._rows(X)
         self._vector(coef, self.coefLen, "coef")
         new = lambda want, *shape: (torch.empty(shape, dtype=torch.float64, device=X.device)
                                     if want else None)          # noqa: E731
         mg, r, q, p = new(margin, n), new(raw, n, 2), new(prob, n, 2), new(pred, n)
         with torch.cuda.device(X.device):
+            if isinstance(X, FMSparseRows):
+                N.check(self._lib.cyc_fmcsr_predict_dev(
+                    self.handle, X.handle, N.ptr(coef), N.ptr(mg), N.ptr(r), N.ptr(q), N.ptr(p),
+                    N.stream_handle()))
+                return mg, r, q, p
             N.check(self._lib.cyc_fm_predict_dev(self.handle, N.ptr(X), n, N.ptr(coef), N.ptr(mg),
                                                  N.ptr(r), N.ptr(q), N.ptr(p), N.stream_handle()))
         return mg, r, q, p
@@ -268,15 +325,15 @@ class FMDeviceStep:
                  fitLinear: bool = True, fraction: float = 1.0, workspaceBytes: int = 0):
         import torch
         from . import parallel
-        from .linalg import CSRRows
-        if isinstance(X, CSRRows):
-            raise N.IllegalArgumentException("FM takes dense rows; the CSR form is not provided")
-        _require(torch.is_tensor(X) and X.dim() == 2, "rows must be a device tensor (n x d)")
+        X = as_rows(X)                  # a CSR shard is prepared here, once
+        sparse = isinstance(X, FMSparseRows)
+        _require(sparse or (torch.is_tensor(X) and X.dim() == 2),
+                 "rows must be a device tensor (n x d), CSRRows or FMSparseRows")
+        n, d = (X.n, X.d) if sparse else (int(v) for v in X.shape)
         self.X, self.y, self.fraction = X, y, float(fraction)
-        self.plan = FMPlan(int(X.shape[1]), factorSize, fitIntercept, fitLinear, loss,
-                           workspaceBytes)
+        self.plan = FMPlan(d, factorSize, fitIntercept, fitLinear, loss, workspaceBytes)
         self.d, self.k = self.plan.d, self.plan.k
-        sizes = parallel.allgather_object(int(X.shape[0]))
+        sizes = parallel.allgather_object(n)
         self.rowOffset = int(sum(sizes[:parallel.world()[0]])) if len(sizes) > 1 else 0
         self.out = torch.empty(self.plan.coefLen + 2, dtype=torch.float64, device=X.device)
 
@@ -401,8 +458,8 @@ class _FMModel:
         import torch
         if self._plan is None:
             self._plan = FMPlan(self.numFeatures, self.factorSize, True, True, self.LOSS)
-        n = self._plan._rows(X)
-        del n
+        X = as_rows(X)
+        self._plan._rows(X)
         if self._coef is None or self._coef.device != X.device:
             flat = np.concatenate([self.factors.ravel(), self.linear, [self.intercept]])
             self._coef = torch.from_numpy(flat).to(X.device)

@@ -1159,7 +1159,7 @@ int cyc_gbt_predict_dev(cyc_gbt_plan plan, const double* X, int64_t nrows, int32
 /* One evaluation of the factorization machine's loss and gradient
  * (ml/regression/FMRegressor.scala, BaseFactorizationMachinesGradient) over
  * dense fp64 device rows, and the models' forward.  A plan holds numFeatures
- * d (1 .. cyc_fm_max_features), factorSize k (1 .. cyc_fm_max_factors), the
+ * d (>= 1; the dense calls take 1 .. cyc_fm_max_features), factorSize k (1 .. cyc_fm_max_factors), the
  * two fit flags, the loss (0 squared, 1 logistic with labels 0 / 1) and the
  * scratch of the calls (workspaceBytes for the runs in flight; 0: 256 MiB).
  *
@@ -1203,6 +1203,44 @@ int cyc_fm_evaluate_dev(cyc_fm_plan plan, const double* X, const double* y, int6
                         double* out, void* stream);
 int cyc_fm_predict_dev(cyc_fm_plan plan, const double* X, int64_t nrows, const double* coef,
                        double* margin, double* raw, double* prob, double* pred, void* stream);
+
+/* The same evaluation and forward over CSR rows (csrc/fm_csr.hip), for any
+ * numFeatures up to 2^31 - 1: cyc_fm_plan_create takes every d >= 1 and only
+ * the two dense calls above refuse d > cyc_fm_max_features.
+ *
+ * cyc_fmcsr_rows_create prepares one shard once, outside the loop: rowptr
+ * (int64, nrows + 1, rowptr[0] == 0), colidx (int32, strictly increasing in a
+ * row, in [0, numFeatures); SparseVector's messages otherwise) and values
+ * (fp64) on the device, nrows < 2^31, any nnz.  The three arrays are borrowed
+ * and must outlive the handle.  The handle owns a column-major copy (per
+ * column: row int32 and value fp64, rows ascending, one row block, colptr
+ * int64[numFeatures + 1]) and a segment table: a column of more than
+ * cyc_fmcsr_segment_entries entries is cut into segments of exactly that many
+ * (the last one shorter).  It synchronizes the stream.
+ *
+ * cyc_fmcsr_evaluate_dev SETS out as cyc_fm_evaluate_dev does, same batch
+ * rule, same label check; a stored zero contributes nothing.  A row's sums
+ * run over its non-zeros i = slot, slot + S, .. (S = 64 / KP slots, KP the
+ * power of two >= k), the slots added in slot order; a column's sums run over
+ * its rows in ascending order (a long column: per segment, quarter and lane
+ * group, added in that fixed order, the segments in segment order); gb, L and
+ * cnt over runs of cyc_fm_run_rows rows in run order.  No order depends on the
+ * grid, the workspace or the call: out has the same bytes on every call.  The
+ * plan's scratch grows to nrows (k + 3) + segments (k + 2) doubles
+ * (workspaceBytes is not consulted).  cyc_fmcsr_predict_dev writes what
+ * cyc_fm_predict_dev writes and does not synchronize. */
+typedef struct cyc_fmcsr_rows_s* cyc_fmcsr_rows;
+
+int cyc_fmcsr_segment_entries(void);
+int cyc_fmcsr_rows_create(const int64_t* rowptr, const int32_t* colidx, const double* values,
+                          int64_t nrows, int32_t numFeatures, void* stream,
+                          cyc_fmcsr_rows* rows);
+int cyc_fmcsr_rows_destroy(cyc_fmcsr_rows rows);
+int cyc_fmcsr_evaluate_dev(cyc_fm_plan plan, cyc_fmcsr_rows rows, const double* y,
+                           const double* coef, int64_t iter, double fraction, int64_t rowOffset,
+                           double* out, void* stream);
+int cyc_fmcsr_predict_dev(cyc_fm_plan plan, cyc_fmcsr_rows rows, const double* coef,
+                          double* margin, double* raw, double* prob, double* pred, void* stream);
 
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
