@@ -67,6 +67,7 @@ from .fm import (  # noqa: F401
     FMRegressor,
     FMSparseRows,
 )
+from .lda import LDA, LDAPlan, LocalLDAModel  # noqa: F401
 from .regression_summary import (  # noqa: F401
     LinearRegressionSummary,
     LinearRegressionTrainingSummary,

@@ -200,6 +200,20 @@ SIGNATURES = {
     "cyc_fmcsr_rows_destroy": (ctypes.c_int, [_vp]),
     "cyc_fmcsr_evaluate_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _f64, _i64, _vp, _vp]),
     "cyc_fmcsr_predict_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_lda_max_topics": (ctypes.c_int, []),
+    "cyc_lda_slab_bytes": (ctypes.c_int, []),
+    "cyc_lda_segment_entries": (ctypes.c_int, []),
+    "cyc_lda_run_docs": (ctypes.c_int, []),
+    "cyc_lda_topic_stride": (ctypes.c_int, [_i32]),
+    "cyc_lda_docs_create": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, ctypes.POINTER(_vp)]),
+    "cyc_lda_docs_destroy": (ctypes.c_int, [_vp]),
+    "cyc_lda_plan_create": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_vp)]),
+    "cyc_lda_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_lda_set_topics_dev": (ctypes.c_int, [_vp, _vp, _vp]),
+    "cyc_lda_infer_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "cyc_lda_estep_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "cyc_lda_bound_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cyc_lda_digamma_dev": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
     "cyc_gmm_plan_create": (ctypes.c_int, [_i32, _i32, _i64, ctypes.POINTER(_vp)]),
     "cyc_gmm_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_gmm_set_model_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

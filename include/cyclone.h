@@ -1242,6 +1242,80 @@ int cyc_fmcsr_evaluate_dev(cyc_fm_plan plan, cyc_fmcsr_rows rows, const double* 
 int cyc_fmcsr_predict_dev(cyc_fm_plan plan, cyc_fmcsr_rows rows, const double* coef,
                           double* margin, double* raw, double* prob, double* pred, void* stream);
 
+/* ------------------------------------------------------------------ LDA */
+/* The E step of online variational Bayes for latent Dirichlet allocation
+ * (mllib/clustering/LDAOptimizer.scala, OnlineLDAOptimizer; LDAModel.scala,
+ * LocalLDAModel) over CSR documents of term counts (csrc/lda.hip), 1 <= k <=
+ * cyc_lda_max_topics topics, any vocabSize up to 2^31 - 1.
+ *
+ * psi is digamma and E(v)_t = psi(v_t) - psi(sum v).  cyc_lda_set_topics_dev
+ * takes lambda (device, k x vocabSize row-major) and keeps E(lambda) (per topic
+ * row; the row sums in a fixed order) and B = exp(E(lambda)), both stored
+ * vocabSize x k.  Per document d with at least one non-zero count and a
+ * non-zero weight, ids / cts its stored words and counts, from gamma = gamma0_d:
+ *
+ *   e = exp(E(gamma));  phi = B[ids] e + 1e-100
+ *   repeat:  last = gamma;  gamma = e o (B[ids]^T (cts / phi)) + alpha
+ *            e = exp(E(gamma));  phi = B[ids] e + 1e-100;  it += 1
+ *   until not (sum|gamma - last| / k > 1e-3) or it == maxInner
+ *
+ * maxInner >= 1 bounds the loop (the reference has no cap).  Every other
+ * document (no stored entry, only stored zeros, or weight 0) gets a gamma row
+ * of zeros and it = 0 and contributes nothing.  weights (ndocs, NULL: all 1)
+ * multiply a document's contributions; gamma0 and gamma are ndocs x k, alpha
+ * is k, iters (int32, ndocs; may be NULL) the sweeps taken.
+ *
+ * cyc_lda_docs_create prepares one shard once: rowptr (int64, ndocs + 1,
+ * rowptr[0] == 0), colidx (int32, strictly increasing in a document, in [0,
+ * vocabSize); SparseVector's messages otherwise) and counts (fp64, none
+ * negative or NaN) on the device, ndocs < 2^31.  The arrays are borrowed and
+ * must outlive the handle.  The handle owns the column copy (per word its
+ * documents ascending) with a segment table (a word of more than
+ * cyc_lda_segment_entries documents is cut into segments of that many) and
+ * the documents' order by stored length.  It synchronizes the stream.
+ *
+ * Topic stride KS = cyc_lda_topic_stride(k): the power of two >= k up to 64,
+ * then 64 ceil(k / 64).  A document of at most cyc_lda_slab_bytes / (8 KS)
+ * stored words keeps its rows of B in LDS for all sweeps; a longer one reads
+ * them from L2 in chunks of 64 words every sweep.  Both give the same bytes.
+ *
+ * cyc_lda_infer_dev writes gamma and iters.  cyc_lda_estep_dev does the same
+ * (gamma may be NULL there) and SETS out (device, k vocabSize + k + 1) = [stat
+ * (k x vocabSize) | logphat (k) | nonEmpty]: stat[t, v] = B[v, t] sum over the
+ * documents d holding v, ascending, of w_d e_dt cts_dv / phi_dv (e and phi as
+ * the loop ended), logphat_t = sum_d w_d E(gamma_d)_t, nonEmpty = sum_d w_d,
+ * the last two over runs of cyc_lda_run_docs documents added in run order.
+ * cyc_lda_bound_dev SETS out[0] = sum_d w_d [ sum_v cts_dv logsumexp_t(
+ * E(gamma_d)_t + E(lambda)_tv) + sum_t (alpha_t - gamma_dt) E(gamma_d)_t +
+ * sum_t (lgamma(gamma_dt) - lgamma(alpha_t)) + lgamma(sum alpha) - lgamma(sum_t
+ * gamma_dt) ] over the same documents, from a gamma of cyc_lda_infer_dev.
+ * No floating-point atomics, no order that depends on the grid or the call:
+ * the same bytes on every call.  The calls do not synchronize.
+ * cyc_lda_digamma_dev: out[i] = the kernels' psi(x[i]) (x > 0; NaN otherwise). */
+typedef struct cyc_lda_docs_s* cyc_lda_docs;
+typedef struct cyc_lda_plan_s* cyc_lda_plan;
+
+int cyc_lda_max_topics(void);
+int cyc_lda_slab_bytes(void);
+int cyc_lda_segment_entries(void);
+int cyc_lda_run_docs(void);
+int cyc_lda_topic_stride(int32_t k);
+int cyc_lda_docs_create(const int64_t* rowptr, const int32_t* colidx, const double* counts,
+                        int64_t ndocs, int32_t vocabSize, void* stream, cyc_lda_docs* docs);
+int cyc_lda_docs_destroy(cyc_lda_docs docs);
+int cyc_lda_plan_create(int32_t k, int32_t vocabSize, cyc_lda_plan* plan);
+int cyc_lda_plan_destroy(cyc_lda_plan plan);
+int cyc_lda_set_topics_dev(cyc_lda_plan plan, const double* lambda, void* stream);
+int cyc_lda_infer_dev(cyc_lda_plan plan, cyc_lda_docs docs, const double* alpha,
+                      const double* gamma0, const double* weights, int32_t maxInner,
+                      double* gamma, int32_t* iters, void* stream);
+int cyc_lda_estep_dev(cyc_lda_plan plan, cyc_lda_docs docs, const double* alpha,
+                      const double* gamma0, const double* weights, int32_t maxInner,
+                      double* gamma, int32_t* iters, double* out, void* stream);
+int cyc_lda_bound_dev(cyc_lda_plan plan, cyc_lda_docs docs, const double* alpha,
+                      const double* gamma, const double* weights, double* out, void* stream);
+int cyc_lda_digamma_dev(const double* x, int64_t n, double* out, void* stream);
+
 /* ------------------------------------------------------------------ ALS */
 /* One half-step of ml/recommendation/ALS.scala's computeFactors
  * (NormalEquation.add per rating, CholeskySolver.solve per destination id)
