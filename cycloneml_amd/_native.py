@@ -107,6 +107,14 @@ SIGNATURES = {
     "cyc_rowmatrix_multiply_dev": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "cyc_rowmatrix_multiply_csr_dev": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp,
                                                       _vp]),
+    "cyc_tsqr_plan_create": (ctypes.c_int, [_i32, _i64, ctypes.POINTER(_vp)]),
+    "cyc_tsqr_plan_destroy": (ctypes.c_int, [_vp]),
+    "cyc_tsqr_run_rows": (ctypes.c_int, []),
+    "cyc_tsqr_tile_rows": (ctypes.c_int, [_i32]),
+    "cyc_tsqr_panel_cols": (ctypes.c_int, []),
+    "cyc_tsqr_factor_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "cyc_tsqr_fold_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "cyc_tsqr_finish_dev": (ctypes.c_int, [_vp, _vp, _vp]),
     "cyc_wls_plan_create": (ctypes.c_int, [_i32, ctypes.POINTER(_vp)]),
     "cyc_wls_plan_destroy": (ctypes.c_int, [_vp]),
     "cyc_wls_accumulate_dev": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

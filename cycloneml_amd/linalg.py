@@ -10,6 +10,8 @@ all-reduce (the treeAggregate combOp U1 += U2, :149-157).  The eigensolve of
 PCA stays on the host (breeze svd on the driver in the reference, :501), and so
 does computeSVD's (:248-390, its local-LAPACK branch); multiply (:400-423) is
 the row-local fp64-MFMA product that applies their result to the rows.
+tallSkinnyQR is the one factorisation that does not go through the Gramian:
+Householder reflectors on the device (csrc/tsqr.hip), R on the host.
 """
 from __future__ import annotations
 
@@ -105,6 +107,70 @@ def triu_to_full(n, U, stream=None):
 
 
 SingularValueDecomposition = namedtuple("SingularValueDecomposition", ["U", "s", "V"])
+QRDecomposition = namedtuple("QRDecomposition", ["Q", "R"])
+
+TSQR_MAX_COLS = 1024
+
+
+class TSQRPlan:
+    """The Householder TSQR of libcyclone (csrc/tsqr.hip) for `ncols` columns.
+    workspaceBytes bounds how many runs go per launch (0: sized per call) and
+    never changes a result."""
+
+    def __init__(self, ncols, workspaceBytes=0):
+        self._lib = N.load()
+        h = ctypes.c_void_p()
+        N.check(self._lib.cyc_tsqr_plan_create(int(ncols), int(workspaceBytes), ctypes.byref(h)))
+        self.handle = h
+        self.n = int(ncols)
+
+    @staticmethod
+    def minWorkspaceBytes(ncols) -> int:
+        """The smallest legal workspace: the running R and one run's."""
+        w = N.load().cyc_tsqr_panel_cols()
+        return 2 * 8 * (-(-int(ncols) // w) * w) ** 2
+
+    def close(self):
+        if self.handle:
+            self._lib.cyc_tsqr_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _out(self, like):
+        return _torch().empty((self.n, self.n), dtype=_torch().float64, device=like.device)
+
+    def factor(self, X, stream=None):
+        """n x n device R of X's rows (signs as the reflectors left them)."""
+        R = self._out(X)
+        N.check(self._lib.cyc_tsqr_factor_dev(self.handle, N.ptr(X), int(X.shape[0]), N.ptr(R),
+                                              N.stream_handle(stream)))
+        return R
+
+    def fold(self, Rs, stream=None):
+        """The R of `Rs` (count x n x n stacked upper triangles), in order."""
+        R = self._out(Rs)
+        N.check(self._lib.cyc_tsqr_fold_dev(self.handle, N.ptr(Rs), int(Rs.shape[0]), N.ptr(R),
+                                            N.stream_handle(stream)))
+        return R
+
+    def finish(self, R, stream=None):
+        N.check(self._lib.cyc_tsqr_finish_dev(self.handle, N.ptr(R), N.stream_handle(stream)))
+        return R
+
+
+def normalize_r_signs(R):
+    """The sign rule of tallSkinnyQR on the host: rows of R with a negative
+    diagonal entry negated (exact), so that every diagonal entry is >= 0."""
+    R = np.array(R, dtype=np.float64)
+    k = min(R.shape)
+    neg = R[np.arange(k), np.arange(k)] < 0
+    R[:k][neg] = -R[:k][neg]
+    return R
 
 
 def svd_from_gramian(G, k: int, rCond: float = 1e-9):
@@ -509,3 +575,63 @@ class RowMatrix:
         s, V = svd_from_gramian(self.computeGramianMatrix(), k, rCond)
         U = self.multiply(V / s) if computeU else None
         return SingularValueDecomposition(U, s, V)
+
+    def tallSkinnyQR(self, computeQ: bool = False, plan: "TSQRPlan | None" = None):
+        """RowMatrix.tallSkinnyQR: QRDecomposition(Q, R) with R (numpy,
+        min(m, n) x n, m the row count over all ranks) upper triangular by
+        Householder reflectors on the device -- never through the Gramian, so
+        its error follows cond(A), not cond(A)^2 -- and Q = A inv(R) by
+        multiply, as the reference forms it (a RowMatrix over this rank's
+        rows; None unless computeQ).  The reference leaves R's signs to LAPACK;
+        here every diagonal entry is >= 0, which makes R unique for a
+        full-rank A.  Every rank calls it: the ranks' R's are gathered and
+        folded in rank order through the same kernel on every rank, so all
+        ranks hold the same bytes.  Dense rows only, n <= 1024."""
+        torch = _torch()
+        if self._sparse:
+            raise N.IllegalArgumentException(
+                "tallSkinnyQR takes dense rows (CSRRows are not densified here)")
+        n = self.numCols()
+        if n > TSQR_MAX_COLS:
+            raise N.IllegalArgumentException(
+                f"tallSkinnyQR supports 1 to {TSQR_MAX_COLS} columns but got {n}")
+        m = self.numRows()
+        if computeQ and m < n:
+            raise N.IllegalArgumentException(
+                f"tallSkinnyQR with computeQ needs numRows >= numCols but got {m} < {n}")
+        X = self.rows
+        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float64
+                and X.dim() == 2 and X.is_contiguous()):
+            raise N.IllegalArgumentException(
+                "tallSkinnyQR takes contiguous fp64 device rows")
+        own = plan is None
+        plan = TSQRPlan(n) if own else plan
+        try:
+            R = plan.factor(X)
+            ranks = parallel.allgather_object(R.cpu().numpy())
+            if len(ranks) > 1:
+                R = plan.fold(torch.from_numpy(np.stack(ranks)).to(self._device))
+            R = plan.finish(R).cpu().numpy()[:min(m, n)]
+        finally:
+            if own:
+                plan.close()
+        Q = None
+        if computeQ:
+            from .regression import SingularMatrixException
+            zero = np.flatnonzero(np.diagonal(R) == 0.0)
+            if zero.size:
+                raise SingularMatrixException(
+                    f"R is singular: its diagonal entry {int(zero[0])} is zero")
+            Q = self.multiply(_upper_inverse(R))
+        return QRDecomposition(Q, R)
+
+
+def _upper_inverse(R):
+    """inv(R) of an upper-triangular R by back substitution, bottom row up."""
+    n = R.shape[0]
+    inv = np.zeros((n, n))
+    for i in range(n - 1, -1, -1):
+        inv[i] = -(R[i, i + 1:] @ inv[i + 1:])
+        inv[i, i] += 1.0
+        inv[i] /= R[i, i]
+    return inv

@@ -372,6 +372,41 @@ int cyc_rowmatrix_multiply_csr_dev(const int64_t* rowptr, const int32_t* colidx,
                                    const double* vals, int64_t nrows, int32_t n, const double* B,
                                    int32_t k, double* Y, void* stream);
 
+/* RowMatrix.tallSkinnyQR (mllib/linalg/distributed/RowMatrix.scala): the R of
+ * X = Q R for dense row-major fp64 rows, 1 <= ncols <= 1024, by Householder
+ * reflectors on fp64 MFMA (csrc/tsqr.hip), never through the Gramian.  The
+ * shard is cut into runs of cyc_tsqr_run_rows() rows counted from row 0 (a
+ * constant: not a function of the device or the workspace); a workgroup folds
+ * its run, in tiles of cyc_tsqr_tile_rows(ncols) rows and panels of
+ * cyc_tsqr_panel_cols() columns, into an R of its own, and the runs' R's are
+ * folded in run order.  workspaceBytes bounds how many runs go per launch (0:
+ * sized per call; otherwise at least two slabs of 8 ceil16(ncols)^2 bytes) and
+ * never changes a result: the same bytes on every call.  No floating-point
+ * atomics.  Non-finite values are not checked; they propagate.
+ *
+ * cyc_tsqr_factor_dev SETS R_out (device, ncols x ncols row-major): upper
+ * triangular with explicit zeros below the diagonal, R^T R = X^T X; the signs
+ * of its rows are the reflectors'.  With nrows < ncols only the first nrows
+ * rows are meaningful.  A column that is zero, or zero after the columns left
+ * of it are eliminated, gets a zero diagonal and no NaN.
+ * cyc_tsqr_fold_dev SETS R_out to the R of `count` stacked ncols x ncols upper
+ * triangles (row-major, entries below the diagonals ignored), folded in index
+ * order: the ranks' R's.  cyc_tsqr_finish_dev negates every row of R whose
+ * diagonal is negative (exact), so that R is the unique factor with a
+ * non-negative diagonal.  The calls do not synchronize. */
+typedef struct cyc_tsqr_plan_s* cyc_tsqr_plan;
+
+int cyc_tsqr_plan_create(int32_t ncols, int64_t workspaceBytes, cyc_tsqr_plan* plan);
+int cyc_tsqr_plan_destroy(cyc_tsqr_plan plan);
+int cyc_tsqr_run_rows(void);
+int cyc_tsqr_tile_rows(int32_t ncols);
+int cyc_tsqr_panel_cols(void);
+int cyc_tsqr_factor_dev(cyc_tsqr_plan plan, const double* X, int64_t nrows, double* R_out,
+                        void* stream);
+int cyc_tsqr_fold_dev(cyc_tsqr_plan plan, const double* Rs, int64_t count, double* R_out,
+                      void* stream);
+int cyc_tsqr_finish_dev(cyc_tsqr_plan plan, double* R, void* stream);
+
 /* ------------------------------------------ WeightedLeastSquares moments */
 /* Replaces WeightedLeastSquares.Aggregator.add (ml/optim/
  * WeightedLeastSquares.scala: spr(w, a, aaSum), axpy(w b, a, abSum),
