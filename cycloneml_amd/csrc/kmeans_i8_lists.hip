@@ -106,25 +106,48 @@ int compact(unsigned int* counts, unsigned int cap, const int32_t* src, int32_t*
 
 namespace {
 
-// The listed rows of a kBndRows-row block in row order: tmp[block *
-// kBndRows ...], their count in bcount[block] (masks: the wave's ballot of
-// `listed` per 256-row step it, wc: IT x 4 counts in LDS)
-constexpr int kBndIT = kBndRows / 256;
-__device__ __forceinline__ void bnd_block_list(const unsigned long long (&masks)[kBndIT],
-                                               unsigned* wc, int64_t base, int32_t* tmp,
-                                               unsigned int* bcount,
-                                               const unsigned long long* flips = nullptr) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  __syncthreads();
+// Both every-row passes below give a lane four consecutive rows per step of
+// 1024 (row base + 4 * (it * 256 + tid) + j), so that the lane's accesses
+// are 16 bytes wide: a kBndRows-row block is kBndIT steps.  A block's lists
+// stay in row order, which is (step, wave, lane, j) lexicographic.
+constexpr int kBndIT = kBndRows / 1024;
+static_assert(kBndRows % 1024 == 0, "a block is whole 1024-row steps");
+
+// own: the lane's four `listed` flags of one step (bit j).  Returns the
+// listed rows of the wave's lower lanes; the wave's count goes to *wcSlot.
+__device__ __forceinline__ unsigned bnd_wave_prefix(unsigned own, unsigned* wcSlot) {
+  const int lane = threadIdx.x & 63;
   const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned pre = 0, tot = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64((own >> j) & 1u);
+    pre += (unsigned)__builtin_popcountll(m & below);
+    tot += (unsigned)__builtin_popcountll(m);
+  }
+  if (lane == 0) *wcSlot = tot;
+  return pre;
+}
+
+// The listed rows of a kBndRows-row block in row order: tmp[block *
+// kBndRows ...], their count in bcount[block] (own / pre: bnd_wave_prefix's
+// input and result per step, wc: kBndIT x 4 wave counts in LDS; flip: the
+// rows listed as ~row)
+__device__ __forceinline__ void bnd_block_list(const unsigned (&own)[kBndIT],
+                                               const unsigned (&pre)[kBndIT], unsigned* wc,
+                                               int64_t base, int32_t* tmp, unsigned int* bcount,
+                                               const unsigned* flip = nullptr) {
+  const int tid = threadIdx.x, wave = tid >> 6;
+  __syncthreads();
 #pragma unroll
   for (int it = 0; it < kBndIT; ++it) {
     unsigned before = 0;
     for (int j = 0; j < it * 4 + wave; ++j) before += wc[j];
-    if ((masks[it] >> lane) & 1ull)
-      tmp[base + before + (unsigned)__builtin_popcountll(masks[it] & below)] =
-          (flips && ((flips[it] >> lane) & 1ull)) ? ~(int32_t)(base + it * 256 + tid)
-                                                  : (int32_t)(base + it * 256 + tid);
+    int64_t pos = base + before + pre[it];
+    const int32_t r0 = (int32_t)(base + 4 * (it * 256 + tid));
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((own[it] >> j) & 1u) tmp[pos++] = (flip && ((flip[it] >> j) & 1u)) ? ~(r0 + j) : r0 + j;
   }
   if (tid == 0) {
     unsigned total = 0;
@@ -133,16 +156,69 @@ __device__ __forceinline__ void bnd_block_list(const unsigned long long (&masks)
   }
 }
 
-// kBndRows rows per workgroup (8 per thread, coalesced): a row keeps its
-// assignment when its moved bounds still certify it (kmeans_i8.hpp Bounds,
-// state 0); else it is re-checked against its carried set when the set's
-// moved outside bound still stands (state 2, listed here), else screened
-// (state 1).  Every carried bound is moved by the drift.  Round 6: a row
-// left for the screen whose center a has a usable neighbourhood (nbrR[a],
-// a lower bound of the distance from c_a to every center outside a and its
-// kCandMax - 1 nearest, over twice the row's moved upper bound, or no
+// One row of the filter.  (a, bx, by, ln): the row's assignment, carried
+// (ub, lb) and carried-set bound; sq = sqrt(P.cmax2).  Returns the state;
+// (nx, ny) are the moved bounds of a kept row (state 0) and nl the carried
+// set's bound to store where one exists (ln >= 0).
+__device__ __forceinline__ int bnd_row(int a, float bx, float by, float ln, const DriftParams& P,
+                                       double sq, int k, const double* __restrict__ delta,
+                                       const float* __restrict__ nbrR, float& nx, float& ny,
+                                       float& nl) {
+  int st = 1;
+  const bool okA = !P.bad && a >= 0 && a < k;
+  if (okA && bx >= 0.0f && by > 0.0f) {
+    const double U = (double)bx + delta[a];
+    const double L = (double)by - (a == P.i1 ? P.d2 : P.d1);
+    // |x| <= |x - c_a| + |c_a| <= U + max |c| (no norm read: 80 MB a
+    // call at 10M rows)
+    const double xr = U + sq;
+    const double xx = xr * xr * (1.0 + 0x1p-50);
+    const double U2 = U * U, L2 = L * L;
+    // the reference's rounding slack, plus this test's own rounding
+    const double tau = 0x1p-29 * (xx + P.cmax2) + 0x1p-48 * (L2 + U2) + 0x1p-1000;
+    if (L > 0.0 && (L2 - U2) > tau) {
+      st = 0;
+      nx = fup(U * (1.0 + 0x1p-50));
+      ny = fdown(L * (1.0 - 0x1p-50));
+    }
+  }
+  // which re-check: a carried set whose moved outside bound still
+  // clears the row's moved upper bound (it will most likely certify);
+  // else the neighbourhood when nbrR[a] exceeds twice that bound (or
+  // the row has none); else a carried set with any margin left.  Both
+  // tests only pick the work: the re-check itself decides.
+  const double Ln = ln >= 0.0f && okA ? ((double)ln - P.d1) * (1.0 - 0x1p-50) : -1.0;
+  const double Um = okA && bx >= 0.0f ? (double)bx + delta[a] : 0.0;
+  if (st == 1 && Ln > 0.0 && Ln > Um) st = 2;
+  if (st == 1 && nbrR && okA) {
+    // (a row without a bound: only when its center moved little
+    // against its neighbourhood -- early in a fit such rows mostly fail)
+    const double R = (double)nbrR[a];
+    if (R > 0.0 && R > 2.0 * Um && (bx >= 0.0f || delta[a] < 0.125 * R)) st = 3;
+  }
+  if (st == 1 && Ln > 0.0) st = 2;
+  // a carried set (NaN / negative: none) is kept while it has a margin
+  nl = (st == 0 || st == 2) && Ln > 0.0 ? fdown(Ln) : -1.0f;
+  return st;
+}
+
+// kBndRows rows per workgroup (8 per thread: two steps of four consecutive
+// rows, one 16-byte load of assign and lnc and two of bnd each): a row keeps
+// its assignment when its moved bounds still certify it (kmeans_i8.hpp
+// Bounds, state 0); else it is re-checked against its carried set when the
+// set's moved outside bound still stands (state 2, listed here), else
+// screened (state 1).  Every carried bound is moved by the drift.  Round 6:
+// a row left for the screen whose center a has a usable neighbourhood
+// (nbrR[a], a lower bound of the distance from c_a to every center outside a
+// and its kCandMax - 1 nearest, over twice the row's moved upper bound, or no
 // bound at all) is re-checked against that neighbourhood instead (state 3,
 // listed as ~row).
+// Stores: bnd changes only for kept rows and lnc only where a carried set
+// exists.  Both are stored 16 bytes wide, the elements the scalar form would
+// have left alone re-stored with the very words that were loaded (moved as
+// integers, never through a float operation), and a 16-byte store none of
+// whose elements changes is skipped.  The four states are one 32-bit store.
+// The last rows of an n that is no multiple of 4 go element by element.
 __global__ __launch_bounds__(256) void k_bounds_filter(const int32_t* __restrict__ assign,
                                                        float2* __restrict__ bnd,
                                                        float* __restrict__ lnc,
@@ -157,65 +233,70 @@ __global__ __launch_bounds__(256) void k_bounds_filter(const int32_t* __restrict
                                                        int32_t* __restrict__ tmp2,
                                                        unsigned int* __restrict__ bcount2) {
   __shared__ unsigned wc[kBndIT * 4], wc2[kBndIT * 4];
-  unsigned long long masks2[kBndIT];
   const DriftParams P = *prm;
-  unsigned long long flips[kBndIT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double sq = __builtin_sqrt(P.cmax2);
+  const int tid = threadIdx.x, wave = tid >> 6;
   const int64_t base = (int64_t)blockIdx.x * kBndRows;
-  unsigned long long masks[kBndIT];
+  unsigned own[kBndIT], flip[kBndIT], own2[kBndIT], pre[kBndIT], pre2[kBndIT];
 #pragma unroll
   for (int it = 0; it < kBndIT; ++it) {
-    const int64_t r = base + it * 256 + tid;
-    int st = 1;
-    if (r < n) {
-      const int a = assign[r];
-      const float2 b = bnd[r];
-      const float ln = lnc[r];
-      const bool okA = !P.bad && a >= 0 && a < k;
-      if (okA && b.x >= 0.0f && b.y > 0.0f) {
-        const double U = (double)b.x + delta[a];
-        const double L = (double)b.y - (a == P.i1 ? P.d2 : P.d1);
-        // |x| <= |x - c_a| + |c_a| <= U + max |c| (no norm read: 80 MB a
-        // call at 10M rows)
-        const double xr = U + __builtin_sqrt(P.cmax2);
-        const double xx = xr * xr * (1.0 + 0x1p-50);
-        const double U2 = U * U, L2 = L * L;
-        // the reference's rounding slack, plus this test's own rounding
-        const double tau = 0x1p-29 * (xx + P.cmax2) + 0x1p-48 * (L2 + U2) + 0x1p-1000;
-        if (L > 0.0 && (L2 - U2) > tau) {
-          st = 0;
-          bnd[r] = make_float2(fup(U * (1.0 + 0x1p-50)), fdown(L * (1.0 - 0x1p-50)));
+    const int64_t r0 = base + 4 * (it * 256 + tid);
+    own[it] = flip[it] = own2[it] = 0u;
+    if (r0 + 3 < n) {
+      const int4 a4 = *reinterpret_cast<const int4*>(assign + r0);
+      uint4 b01 = *reinterpret_cast<const uint4*>(bnd + r0);
+      uint4 b23 = *reinterpret_cast<const uint4*>(bnd + r0 + 2);
+      uint4 l4 = *reinterpret_cast<const uint4*>(lnc + r0);
+      const int a[4] = {a4.x, a4.y, a4.z, a4.w};
+      unsigned bw[8] = {b01.x, b01.y, b01.z, b01.w, b23.x, b23.y, b23.z, b23.w};
+      unsigned lw[4] = {l4.x, l4.y, l4.z, l4.w};
+      unsigned sw = 0u, kept = 0u, carried = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float ln = __uint_as_float(lw[j]);
+        float nx = 0.0f, ny = 0.0f, nl = 0.0f;
+        const int st = bnd_row(a[j], __uint_as_float(bw[2 * j]), __uint_as_float(bw[2 * j + 1]),
+                               ln, P, sq, k, delta, nbrR, nx, ny, nl);
+        if (st == 0) {
+          bw[2 * j] = __float_as_uint(nx);
+          bw[2 * j + 1] = __float_as_uint(ny);
+          kept |= 1u << j;
         }
+        if (ln >= 0.0f) {
+          lw[j] = __float_as_uint(nl);
+          carried |= 1u << j;
+        }
+        sw |= (unsigned)st << (8 * j);
+        own[it] |= (st >= 2 ? 1u : 0u) << j;
+        flip[it] |= (st == 3 ? 1u : 0u) << j;
+        own2[it] |= (st == 1 ? 1u : 0u) << j;
       }
-      // which re-check: a carried set whose moved outside bound still
-      // clears the row's moved upper bound (it will most likely certify);
-      // else the neighbourhood when nbrR[a] exceeds twice that bound (or
-      // the row has none); else a carried set with any margin left.  Both
-      // tests only pick the work: the re-check itself decides.
-      const double Ln = ln >= 0.0f && okA ? ((double)ln - P.d1) * (1.0 - 0x1p-50) : -1.0;
-      const double Um = okA && b.x >= 0.0f ? (double)b.x + delta[a] : 0.0;
-      if (st == 1 && Ln > 0.0 && Ln > Um) st = 2;
-      if (st == 1 && nbrR && okA) {
-        // (a row without a bound: only when its center moved little
-        // against its neighbourhood -- early in a fit such rows mostly fail)
-        const double R = (double)nbrR[a];
-        if (R > 0.0 && R > 2.0 * Um && (b.x >= 0.0f || delta[a] < 0.125 * R)) st = 3;
+      if (kept & 3u)
+        *reinterpret_cast<uint4*>(bnd + r0) = make_uint4(bw[0], bw[1], bw[2], bw[3]);
+      if (kept & 12u)
+        *reinterpret_cast<uint4*>(bnd + r0 + 2) = make_uint4(bw[4], bw[5], bw[6], bw[7]);
+      if (carried) *reinterpret_cast<uint4*>(lnc + r0) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
+      *reinterpret_cast<unsigned*>(state + r0) = sw;
+    } else {
+      for (int j = 0; j < 4 && r0 + j < n; ++j) {
+        const int64_t r = r0 + j;
+        const float2 b = bnd[r];
+        const float ln = lnc[r];
+        float nx = 0.0f, ny = 0.0f, nl = 0.0f;
+        const int st = bnd_row(assign[r], b.x, b.y, ln, P, sq, k, delta, nbrR, nx, ny, nl);
+        if (st == 0) bnd[r] = make_float2(nx, ny);
+        if (ln >= 0.0f) lnc[r] = nl;
+        state[r] = (unsigned char)st;
+        own[it] |= (st >= 2 ? 1u : 0u) << j;
+        flip[it] |= (st == 3 ? 1u : 0u) << j;
+        own2[it] |= (st == 1 ? 1u : 0u) << j;
       }
-      if (st == 1 && Ln > 0.0) st = 2;
-      if (ln >= 0.0f)   // a carried set (NaN / negative: none) kept while it has a margin
-        lnc[r] = (st == 0 || st == 2) && Ln > 0.0 ? fdown(Ln) : -1.0f;
-      state[r] = (unsigned char)st;
     }
-    masks[it] = __builtin_amdgcn_ballot_w64(st >= 2);
-    flips[it] = __builtin_amdgcn_ballot_w64(st == 3);
-    masks2[it] = __builtin_amdgcn_ballot_w64(r < n && st == 1);
-    if (lane == 0) {
-      wc[it * 4 + wave] = (unsigned)__builtin_popcountll(masks[it]);
-      wc2[it * 4 + wave] = (unsigned)__builtin_popcountll(masks2[it]);
-    }
+    pre[it] = bnd_wave_prefix(own[it], &wc[it * 4 + wave]);
+    pre2[it] = bnd_wave_prefix(own2[it], &wc2[it * 4 + wave]);
   }
-  bnd_block_list(masks, wc, base, tmp, bcount, flips);
-  if (tmp2) bnd_block_list(masks2, wc2, base, tmp2, bcount2);
+  bnd_block_list(own, pre, wc, base, tmp, bcount, flip);
+  if (tmp2) bnd_block_list(own2, pre2, wc2, base, tmp2, bcount2);
 }
 
 // The rows a full screen takes (state 1), listed as the filter lists its
@@ -224,16 +305,23 @@ __global__ __launch_bounds__(256) void k_bounds_collect(const unsigned char* __r
                                                         int64_t n, int32_t* __restrict__ tmp,
                                                         unsigned int* __restrict__ bcount) {
   __shared__ unsigned wc[kBndIT * 4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, wave = tid >> 6;
   const int64_t base = (int64_t)blockIdx.x * kBndRows;
-  unsigned long long masks[kBndIT];
+  unsigned own[kBndIT], pre[kBndIT];
 #pragma unroll
   for (int it = 0; it < kBndIT; ++it) {
-    const int64_t r = base + it * 256 + tid;
-    masks[it] = __builtin_amdgcn_ballot_w64(r < n && state[r] == 1);
-    if (lane == 0) wc[it * 4 + wave] = (unsigned)__builtin_popcountll(masks[it]);
+    const int64_t r0 = base + 4 * (it * 256 + tid);
+    own[it] = 0u;
+    if (r0 + 3 < n) {
+      const uchar4 s = *reinterpret_cast<const uchar4*>(state + r0);
+      own[it] = (s.x == 1 ? 1u : 0u) | (s.y == 1 ? 2u : 0u) | (s.z == 1 ? 4u : 0u) |
+                (s.w == 1 ? 8u : 0u);
+    } else {
+      for (int j = 0; j < 4 && r0 + j < n; ++j) own[it] |= (state[r0 + j] == 1 ? 1u : 0u) << j;
+    }
+    pre[it] = bnd_wave_prefix(own[it], &wc[it * 4 + wave]);
   }
-  bnd_block_list(masks, wc, base, tmp, bcount);
+  bnd_block_list(own, pre, wc, base, tmp, bcount);
 }
 
 // Single block: bcount[0..nb) -> exclusive offsets, bcount[nb] = *listCount
@@ -298,6 +386,10 @@ int bounds_filter(const Bounds& bd, const FilterArgs& fa, hipStream_t st) {
   const int64_t nb = bounds_blocks(bd.n);
   const bool two = fa.tmp2 && fa.bcount2 && bd.list && bd.listCount;
   if (nb <= 0) return CYC_OK;
+  // k_bounds_filter's 16-byte accesses (the row image's own buffers)
+  CYC_REQUIRE(((uintptr_t)fa.assign | (uintptr_t)bd.ub_lb | (uintptr_t)bd.lnc |
+               (uintptr_t)bd.state) % 16 == 0,
+              "carried bounds: the per-row state must start at 16-byte boundaries");
   KernelTimer timer("k_kmeans_bounds", st);
   int rc;
   if (fa.stats && !fa.nbrsReady &&
@@ -334,6 +426,8 @@ bool recheck_two_phase() {
 int bounds_collect(const Bounds& bd, hipStream_t st) {
   const int64_t nb = bounds_blocks(bd.n);
   if (nb <= 0) return CYC_OK;
+  CYC_REQUIRE((uintptr_t)bd.state % 16 == 0,
+              "carried bounds: the per-row state must start at 16-byte boundaries");
   hipLaunchKernelGGL(k_bounds_collect, dim3((unsigned)nb), dim3(256), 0, st,
                      (const unsigned char*)bd.state, bd.n, bd.tmp, bd.bcount);
   CYC_LAUNCH_CHECK("k_bounds_collect");

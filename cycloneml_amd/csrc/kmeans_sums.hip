@@ -745,43 +745,78 @@ constexpr int kIncMovedFrac = 16;    // at most n / 16 moved rows take the incre
 
 // The rows whose assignment differs from prev (then prev = assign): per
 // kIncRows-row block, in row order, into tmpRow / tmpOld at the block's base;
-// the block's count in bcount[block].
+// the block's count in bcount[block].  A lane takes four consecutive rows
+// per step of 1024 (one 16-byte load of assign and of prev; the last rows of
+// an n that is no multiple of 4 element by element), so row order is (step,
+// wave, lane, j) lexicographic.  prev changes at the moved rows alone, a few
+// in a thousand of a late iteration: those stay 4-byte stores.
 __global__ __launch_bounds__(256) void k_inc_moved(const int32_t* __restrict__ assign,
                                                    int32_t* __restrict__ prev, int64_t n,
                                                    int32_t* __restrict__ tmpRow,
                                                    int32_t* __restrict__ tmpOld,
                                                    unsigned int* __restrict__ bcount) {
-  constexpr int IT = kIncRows / 256;
+  constexpr int IT = kIncRows / 1024;
+  static_assert(kIncRows % 1024 == 0, "a block is whole 1024-row steps");
   __shared__ unsigned wc[IT * 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t base = (int64_t)blockIdx.x * kIncRows;
-  unsigned long long masks[IT];
-  int32_t olds[IT];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned own[IT], pre[IT];   // the lane's moved rows (bit j); those of the wave's lower lanes
+  int32_t olds[IT][4];
 #pragma unroll
   for (int it = 0; it < IT; ++it) {
-    const int64_t r = base + it * 256 + tid;
-    bool moved = false;
-    olds[it] = -1;
-    if (r < n) {
-      const int32_t a = assign[r], b = prev[r];
-      moved = a != b;
-      olds[it] = b;
-      if (moved) prev[r] = a;
+    const int64_t r0 = base + 4 * (it * 256 + tid);
+    own[it] = 0u;
+    if (r0 + 3 < n) {
+      const int4 a4 = *reinterpret_cast<const int4*>(assign + r0);
+      const int4 b4 = *reinterpret_cast<const int4*>(prev + r0);
+      const int32_t a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        olds[it][j] = b[j];
+        if (a[j] != b[j]) {
+          own[it] |= 1u << j;
+          prev[r0 + j] = a[j];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        olds[it][j] = -1;
+        if (r0 + j < n) {
+          const int32_t a = assign[r0 + j], b = prev[r0 + j];
+          olds[it][j] = b;
+          if (a != b) {
+            own[it] |= 1u << j;
+            prev[r0 + j] = a;
+          }
+        }
+      }
     }
-    masks[it] = __builtin_amdgcn_ballot_w64(moved);
-    if (lane == 0) wc[it * 4 + wave] = (unsigned)__builtin_popcountll(masks[it]);
+    unsigned tot = 0;
+    pre[it] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long m = __builtin_amdgcn_ballot_w64((own[it] >> j) & 1u);
+      pre[it] += (unsigned)__builtin_popcountll(m & below);
+      tot += (unsigned)__builtin_popcountll(m);
+    }
+    if (lane == 0) wc[it * 4 + wave] = tot;
   }
   __syncthreads();
-  const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
   for (int it = 0; it < IT; ++it) {
     unsigned before = 0;
     for (int j = 0; j < it * 4 + wave; ++j) before += wc[j];
-    if ((masks[it] >> lane) & 1ull) {
-      const int64_t pos = base + before + (unsigned)__builtin_popcountll(masks[it] & below);
-      tmpRow[pos] = (int32_t)(base + it * 256 + tid);
-      tmpOld[pos] = olds[it];
-    }
+    int64_t pos = base + before + pre[it];
+    const int32_t r0 = (int32_t)(base + 4 * (it * 256 + tid));
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((own[it] >> j) & 1u) {
+        tmpRow[pos] = r0 + j;
+        tmpOld[pos] = olds[it][j];
+        ++pos;
+      }
   }
   if (tid == 0) {
     unsigned total = 0;
@@ -1388,6 +1423,9 @@ int inc_accumulate(SortScratch& s, IncState& inc, const double* X, const double*
       (rc = inc.bad.reserve(sizeof(int) * (size_t)k)) || (rc = inc.tot.reserve(64)) ||
       (rc = inc.cum.reserve(64)))
     return rc;
+  // k_inc_moved loads both 16 bytes wide
+  CYC_REQUIRE(((uintptr_t)assign | (uintptr_t)inc.prev.ptr) % 16 == 0,
+              "incremental sums: the assignments must start at a 16-byte boundary");
   if (fresh) {
     CYC_HIP(hipMemsetAsync(inc.prev.ptr, 0xff, sizeof(int32_t) * (size_t)n, st));
     CYC_HIP(hipMemsetAsync(inc.cum.ptr, 0, 16, st));
